@@ -33,6 +33,12 @@ in the loop.
 
 Prints ONE JSON line (see the driver contract).  value = points entering
 the forward+inverse pass per second, whole job.
+
+--dump-outputs DIR writes what the LAST timed step of the headline left with
+its caller -- coefficients, encoder reconstruction, decoder output of this
+rank's frames -- as DIR/<name>.npy (dump_outputs).  The frames are generated
+from fixed seeds, so two builds run with the same arguments are compared
+output for output.
 """
 import argparse
 import json
@@ -46,6 +52,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s measured with a float4 copy)
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files of one run together
 
 
 def parse():
@@ -77,6 +84,8 @@ def parse():
                     help="frames per GPU of the weak_batched leg (the regime where one GPU is busy)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the alternative-flag, 10M-forward, calibration and lifting legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step of the headline as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -185,6 +194,19 @@ def to_device(torch, array, dev):
     if dev.type == "cuda" and t.numel():
         t = t.pin_memory()
     return t.to(dev)
+
+
+def dump_outputs(torch, path, tensors, suffix=""):
+    """--dump-outputs: one float64 .npy per tensor (float64 holds every int32 exactly), DUMP_BUDGET_BYTES for all of
+    them together.  A tensor over its share is cut down to a sample of its elements drawn with a fixed seed -- the same
+    elements in every run, in ascending order of their index."""
+    os.makedirs(path, exist_ok=True)
+    cap = (DUMP_BUDGET_BYTES // len(tensors) - 128) // 8  # (128 bytes: the .npy header)
+    for name, t in tensors.items():
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            t = t[to_device(torch, idx, t.device)]
+        np.save(os.path.join(path, name + suffix + ".npy"), t.cpu().numpy().astype(np.float64))
 
 
 def main():
@@ -318,6 +340,14 @@ def main():
     # in-run sanity: decoder output == encoder reconstruction (the
     # reference's own conformance criterion)
     roundtrip_ok = b.roundtrip_ok() if args.direction != "forward" else None
+    if args.dump_outputs:
+        # now: the legs below run other parameter sets over the same buffers
+        last = {}
+        if args.direction in ("both", "forward"):
+            last.update(coefficients=b.d_coeffs, reconstruction=b.d_attrs)
+        if args.direction in ("both", "inverse"):
+            last.update(decoded=b.d_dec)
+        dump_outputs(torch, args.dump_outputs, last, f"_rank{rank}" if world > 1 else "")
     ms_per_step = elapsed / args.steps * 1e3
     value = n * world * args.steps / elapsed / 1e6
     dir_name = {"both": "forward+inverse", "forward": "forward only", "inverse": "inverse only"}[args.direction]

@@ -37,26 +37,29 @@ def run_bench(world, points, c3, c4):
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_share_the_gpu():
-    """the node's size: eight ranks (here sharing one device, gather through host memory) -- rendezvous, per-rank
-    frames, the gather, configs[3]'s frames and configs[4]'s ten slices sharded 2,2,1,1,1,1,1,1"""
-    d = run_bench(8, 60000, 50000, 40000)
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak"
-    assert d["distributed"]["world_size"] == 8
+def test_bench_four_ranks_share_the_gpu():
+    """four ranks (here sharing one device, gather through host memory) -- rendezvous, per-rank frames, the gather,
+    configs[3]'s frames and configs[4]'s ten slices, which do not divide evenly: sharded 3,3,2,2.  Four and
+    not the node's eight: a GPU that other people's work shares takes only a few processes at a time, and pytest itself
+    holds it as well; the eight-rank shapes of the sharding (2,2,1,1,1,1,1,1, ranks without a unit) are pinned without a
+    GPU by test_sharding_gloo.py."""
+    d = run_bench(4, 60000, 50000, 40000)
+    assert d["n_gpus"] == 4 and d["scaling"] == "weak"
+    assert d["distributed"]["world_size"] == 4
     assert d["config"]["roundtrip_decoder_equals_encoder_recon"] is True
     assert d["config"]["gathered_equals_single_rank"] is True
     assert d["configs3"]["roundtrip_decoder_equals_encoder_recon"] is True
     c4 = d["configs4"]
-    assert c4["scaling"] == "strong" and sorted(c4["slices_per_rank"]) == [1, 1, 1, 1, 1, 1, 2, 2]
-    assert c4["ceiling"].startswith("at most 5.00x")
+    assert c4["scaling"] == "strong" and sorted(c4["slices_per_rank"]) == [2, 2, 3, 3]
+    assert c4["ceiling"].startswith("at most 3.33x")
     assert c4["roundtrip_decoder_equals_encoder_recon"] is True and c4["gathered_equals_single_rank"] is True
     assert c4["value"] > 0
     # the throughput regime of the weak-scaling line: several frames per GPU and step, per-rank device and gather times
     wb = d["weak_batched"]
     assert wb["frames_per_gpu"] == 3 and wb["scaling"] == "weak" and wb["value"] > 0
     assert wb["roundtrip_decoder_equals_encoder_recon"] is True
-    assert len(wb["device_ms_per_rank"]) == 8 and len(wb["gather_ms_per_rank"]) == 8
-    assert len(d["distributed"]["device_ms_per_rank"]) == 8 and min(d["distributed"]["device_ms_per_rank"]) > 0
+    assert len(wb["device_ms_per_rank"]) == 4 and len(wb["gather_ms_per_rank"]) == 4
+    assert len(d["distributed"]["device_ms_per_rank"]) == 4 and min(d["distributed"]["device_ms_per_rank"]) > 0
 
 
 @pytest.mark.gpu

@@ -225,10 +225,20 @@ def test_neighbour_links_opt_in(subnode, ctx, monkeypatch):
     records instead of bisecting -- measured slower on the MI355X (profiles/r05_links_ab.txt) and therefore off by
     default, but bit-exact: the golden cases that use the RAHT extension, multi-slice batches, several search ranges
     (the window is an index distance at the consumer)"""
-    from mpeg_pcc_tmc13_amd import _lib, raht_params, synth
+    from mpeg_pcc_tmc13_amd import _lib, build, raht_params, synth
     if not _lib.load().gpcc_debug_has_experiments():
-        pytest.skip("the library was built without -DGPCC_EXPERIMENTS=1 (the default: the experiments' branches cost "
-                    "the headline kernel 1.6 %); the emulator tier pins the links")
+        # the product library leaves the experiments' branches out (they cost the headline kernel 1.6 %): this test
+        # runs in a fresh process on the experiments build that build() makes next to it
+        import os
+        import subprocess
+        import sys
+        assert _lib.LIB_PATH != build.LIB_EXPERIMENTS, "the experiments build lacks the experiments"
+        assert os.path.exists(build.LIB_EXPERIMENTS), build.LIB_EXPERIMENTS + " is missing: run build()"
+        r = subprocess.run([sys.executable, "-m", "pytest", f"{__file__}::test_neighbour_links_opt_in[{subnode}]", "-q",
+                            "-m", "gpu"], env=dict(os.environ, GPCC_LIB_PATH=build.LIB_EXPERIMENTS),
+                           capture_output=True, text=True, timeout=900, cwd=os.path.dirname(os.path.dirname(__file__)))
+        assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+        return
     monkeypatch.setenv("GPCC_LINKS", "1")   # (read by the library at every call)
     o = ol.oracle()
     for kind, n, c, sr in (("dense", 60000, 3, 50000), ("lidar", 90000, 1, 2500), ("dense", 30000, 1, 8), ("lidar", 50000, 1, 8)):

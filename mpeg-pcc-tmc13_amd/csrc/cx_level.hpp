@@ -249,43 +249,6 @@ cx_coeffs(
   *sqw = cx_sqrt_from_rsqrt(w, rs, L);
 }
 
-// rdoq_threshold() of raht_levels.hpp with the reciprocal of lambda at hand
-__device__ __forceinline__ uint32_t
-cx_rdoq_threshold(int64_t dist2, int64_t lambda, double inv_lambda, int rate_coeff, uint32_t limit)
-{
-  const uint64_t d = (uint64_t)dist2 << 26;
-  const uint64_t lam = (uint64_t)lambda;
-  const int rc = (rate_coeff + 128) >> 8;
-  constexpr uint64_t kCap = 128;
-  uint64_t q = kCap;
-  if (d < lam * kCap) {
-    q = (uint64_t)((double)d * inv_lambda);
-    q -= q * lam > d;
-    q += (q + 1) * lam <= d;
-  }
-  const int m = (int)q - rc + 1;  // smallest rate that passes
-  if (m <= 1)
-    return 0;
-  if (m <= 2)
-    return 1;
-  if (m <= 3)
-    return 2;
-  if (m <= 5)
-    return 3;
-  if (m <= 7)
-    return 5;
-  if (m <= 9)
-    return 7;
-  if (m <= 11)
-    return 9;
-  int bb = (m - 12 + 1) >> 1;
-  bb = bb < 1 ? 1 : bb;
-  if (bb > 30)
-    return kDescNever;
-  const uint32_t tz = 10u + (1u << (bb - 1));
-  return tz > limit ? kDescNever : tz;
-}
-
 __device__ __forceinline__ void
 cx_fill_quant(ParamsConst prm, const LevelSched& e, int c, CxQuant* qt, int entry)
 {
@@ -862,7 +825,7 @@ cx_level_tile(const CxCtx& cx, CxSmem& sm, int li, int tile)
       }
       d = kDescNever;
       if (sum_coeff < 3) {
-        d = cx_rdoq_threshold(dist2, lambda, inv_lambda, rate_coeff, (uint32_t)sl.n_s);
+        d = rdoq_threshold_recip(dist2, lambda, inv_lambda, rate_coeff, (uint32_t)sl.n_s);
         if (sum_coeff == 0)
           d |= kDescZero;
       }

@@ -319,25 +319,19 @@ rate_log_small(int64_t aq)
 // Smallest zero-run length for which RDOQ zeroes a coefficient
 // (tmc3/RAHT.cpp:1617-1637).  The rate term is a non-decreasing step
 // function of trainZeros: LUTbins for 0..10, then 12 + 2*bitlen(tz - 10).
+// Every class test is  d < lambda * (rate + rc)  with integers, i.e.
+// floor(d / lambda) < rate + rc: ONE exact quotient q decides them all (the
+// literal form walked up to 37 classes, a 64-bit multiply each, and sat on
+// the dependency chain of the sub-node encoder).  q is capped where no
+// class is left; below the cap d < 2^57, the double quotient is within one
+// of the truth and two integer checks make it exact.
+constexpr uint64_t kRdoqCap = 128;  // > 12 + 2 * 30 + rc for every rc the LUT can give (<= 12)
+
+// ... from the exact (capped) quotient
 __device__ __forceinline__ uint32_t
-rdoq_threshold(int64_t dist2, int64_t lambda, int rate_coeff, uint32_t limit)
+rdoq_threshold_of_quotient(uint64_t q, int rate_coeff, uint32_t limit)
 {
-  // Every class test is  d < lambda * (rate + rc)  with integers, i.e.
-  // floor(d / lambda) < rate + rc: ONE exact quotient q decides them all (the
-  // literal form walked up to 37 classes, a 64-bit multiply each, and sat on
-  // the dependency chain of the sub-node encoder).  q is capped where no
-  // class is left; below the cap d < 2^57, the double quotient is within one
-  // of the truth and two integer checks make it exact.
-  const uint64_t d = (uint64_t)dist2 << 26;
-  const uint64_t lam = (uint64_t)lambda;
   const int rc = (rate_coeff + 128) >> 8;
-  constexpr uint64_t kCap = 128;  // > 12 + 2 * 30 + rc for every rc the LUT can give (<= 12)
-  uint64_t q = kCap;
-  if (d < lam * kCap) {
-    q = (uint64_t)((double)d / (double)lam);
-    q -= q * lam > d;
-    q += (q + 1) * lam <= d;
-  }
   const int m = (int)q - rc + 1;  // smallest rate that passes
   if (m <= 1)
     return 0;
@@ -360,6 +354,38 @@ rdoq_threshold(int64_t dist2, int64_t lambda, int rate_coeff, uint32_t limit)
     return kDescNever;
   const uint32_t tz = 10u + (1u << (bb - 1));
   return tz > limit ? kDescNever : tz;
+}
+
+__device__ __forceinline__ uint32_t
+rdoq_threshold(int64_t dist2, int64_t lambda, int rate_coeff, uint32_t limit)
+{
+  const uint64_t d = (uint64_t)dist2 << 26;
+  const uint64_t lam = (uint64_t)lambda;
+  uint64_t q = kRdoqCap;
+  if (d < lam * kRdoqCap) {
+    q = (uint64_t)((double)d / (double)lam);
+    q -= q * lam > d;
+    q += (q + 1) * lam <= d;
+  }
+  return rdoq_threshold_of_quotient(q, rate_coeff, limit);
+}
+
+// The same with the reciprocal of lambda at hand (lambda is a constant of the quantiser: a kernel that has it
+// before its dependency loop keeps the division off the chain).  The product is within one of the quotient just
+// as the division is -- d and 1 / lambda are each correct to 2^-53 relatively and q < 128 -- and the same two
+// checks make it exact.
+__device__ __forceinline__ uint32_t
+rdoq_threshold_recip(int64_t dist2, int64_t lambda, double inv_lambda, int rate_coeff, uint32_t limit)
+{
+  const uint64_t d = (uint64_t)dist2 << 26;
+  const uint64_t lam = (uint64_t)lambda;
+  uint64_t q = kRdoqCap;
+  if (d < lam * kRdoqCap) {
+    q = (uint64_t)((double)d * inv_lambda);
+    q -= q * lam > d;
+    q += (q + 1) * lam <= d;
+  }
+  return rdoq_threshold_of_quotient(q, rate_coeff, limit);
 }
 
 // Pre-pass of a level, ONE THREAD PER PARENT (64 blocks in flight per

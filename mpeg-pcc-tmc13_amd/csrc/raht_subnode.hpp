@@ -24,10 +24,13 @@
 // finishes the groups whose values have all arrived: normalise, transform,
 // coefficients, inverse, reconstruction.  Children of a neighbour claimed by
 // the SAME wavefront (Morton-adjacent blocks: most hops of the longest
-// chains) are taken from its registers instead.  The poll is the only
-// vector-memory wait inside the loop -- on gfx9 any s_waitcnt vmcnt(0) also
-// waits for the write-through stores in flight.  Spins
-// are bounded: a stuck launch raises ctx.error instead of hanging the GPU.
+// chains) are taken from the wavefront's LDS mailbox instead, and a group fed
+// that way computes while the iteration's poll is in flight: its answer is
+// taken behind the stage bodies, in front of the iteration's first store.
+// The poll is the only vector-memory wait inside the loop -- on gfx9 any
+// s_waitcnt vmcnt(0) also waits for the write-through stores in flight
+// (DESIGN.md section 7).  Spins are bounded: a stuck launch raises ctx.error
+// instead of hanging the GPU.
 //
 // Modes: kSynth (decoder), kFused (integer-Haar encoder) and kLossySub, the
 // lossy encoder.  There the RDOQ zero-run state (tmc3/RAHT.cpp:1618-1669)
@@ -58,15 +61,6 @@ namespace gpcc {
 #endif
 #ifndef GPCC_SUB_DSTORE
 #define GPCC_SUB_DSTORE 0
-#endif
-#ifndef GPCC_SUB_POLL_N
-#define GPCC_SUB_POLL_N 1
-#endif
-#ifndef GPCC_SUB_IDLE_FAST
-#define GPCC_SUB_IDLE_FAST 1
-#endif
-#ifndef GPCC_SUB_IDLE_SPIN
-#define GPCC_SUB_IDLE_SPIN 0
 #endif
 __device__ __forceinline__ int64_t
 sub_round_of_ticket(int tk, int cls)
@@ -190,9 +184,6 @@ store_agent_i64(int64_t* p, int64_t v)
 #ifndef GPCC_SUB_SLEEP
 #define GPCC_SUB_SLEEP 4
 #endif
-#ifndef GPCC_SUB_POLL_RR
-#define GPCC_SUB_POLL_RR 0
-#endif
 #ifndef GPCC_SUB_LOSSY_WAVES
 #define GPCC_SUB_LOSSY_WAVES 3
 #endif
@@ -247,10 +238,24 @@ raht_level_sub_kernel(LevelCtx ctx)
   __shared__ unsigned long long wmail_s[4 * 64 * C];
   unsigned long long* wm = wmail_s + (threadIdx.x >> 6) * (64 * C);
 #endif
-  int pwc12[12];
-#pragma unroll
-  for (int i12 = 0; i12 < 12; i12++)
-    pwc12[i12] = prm->pred_weight_child[i12];
+  // Per-slot state of the 12 child-level neighbours, read by the loop when a lane's slot changes: in LDS, one word
+  // per look-up, instead of 12 registers and a 12-deep select chain each.  nrow_s: row of the awaited child in
+  // rec / mbox, per lane (written and read by the same lane: no barrier).  pwc_s: the neighbour's prediction weight
+  // (prm->pred_weight_child), a copy per wavefront, written here by its own lanes.
+  // (Indexed as arrays: a pointer to them would be a generic one and turn the reads into FLAT.)
+#ifdef GPCC_EMU
+  __shared__ int32_t nrow_s[8][12][256];
+  __shared__ int32_t pwc_s[8 * 4][12];
+#define GPCC_SUB_NROW(i12) nrow_s[blockIdx.x & 7][i12][threadIdx.x]
+#define GPCC_SUB_PWC(i12) pwc_s[(blockIdx.x & 7) * 4 + (threadIdx.x >> 6)][i12]
+#else
+  __shared__ int32_t nrow_s[12][256];
+  __shared__ int32_t pwc_s[4][12];
+#define GPCC_SUB_NROW(i12) nrow_s[i12][threadIdx.x]
+#define GPCC_SUB_PWC(i12) pwc_s[threadIdx.x >> 6][i12]
+#endif
+  if (lane < 12)
+    GPCC_SUB_PWC(lane) = prm->pred_weight_child[lane];
   bool in_range = true;  // (ArithF64: the magnitudes that bound every product, raht_arith.hpp)
   const int cls = blockIdx.x & 7;
 
@@ -716,6 +721,10 @@ raht_level_sub_kernel(LevelCtx ctx)
     if (kLossy && coded)
       qpset_quantizers(prm, e.qp_layer, nq0, nq1, qr);
     const typename A::Quant qra[2] = {A::quant(qr[0]), A::quant(qr[1])};
+    // lambda of the RDOQ decision (tmc3/RAHT.cpp:1617-1637) and its reciprocal: constants of the quantiser, so the
+    // division is done here and not on the chain (rdoq_threshold_recip)
+    const int64_t rd_lambda = (int64_t)qr[0].step * qr[0].step * (C == 1 ? 25 : 35);
+    const double rd_inv_lambda = 1.0 / (double)rd_lambda;
     bool lin_known = false;
     int lin = -1;
     VT dc[C];
@@ -808,8 +817,7 @@ raht_level_sub_kernel(LevelCtx ctx)
         }
       }
     }
-    uint32_t pend = 0;       // neighbours whose child granule is awaited
-    int32_t nrow12[12];      // row of that child in rec / mbox
+    uint32_t pend = 0;       // neighbours whose child granule is awaited (row of that child: GPCC_SUB_NROW)
     // A neighbour block claimed by THIS wavefront in this round (about 70 % of
     // the hops on the longest chains: Morton-adjacent blocks) hands its
     // children over through registers instead of a memory round trip:
@@ -821,7 +829,6 @@ raht_level_sub_kernel(LevelCtx ctx)
       jg[g] = __shfl(on ? j : -1, g << 3);
 #pragma unroll
     for (int i12 = 0; i12 < 12; i12++) {
-      nrow12[i12] = 0;
       const int i = 7 + i12;
       const int owner = gbase | ((i - 1) & 7);
       const int sl = (i - 1) >> 3;
@@ -856,7 +863,7 @@ raht_level_sub_kernel(LevelCtx ctx)
               pred[k] += A::muli(cv, mul);
             }
           } else {
-            nrow12[i12] = (int32_t)nrow;
+            GPCC_SUB_NROW(i12) = (int32_t)nrow;
             pend |= 1u << i12;
             int pg = -1;
 #pragma unroll
@@ -937,17 +944,20 @@ raht_level_sub_kernel(LevelCtx ctx)
     int look = wi - 1;      // look-back cursor
     int outk = 0, outv = -1;   // outgoing RDOQ state: 0 unknown, 1 transparent, 2 final (= outv)
     unsigned long long done = 0;  // children of this round whose value lies in the mailbox (wave-uniform)
-    int poll_last = 31;           // the granule polled last (31: none yet -- start with the lowest awaited one)
     unsigned long long done_seen = ~0ull;  // `done` when the mailbox loop last ran
     int cur_slot = -1, cur_pwc = 0;        // the granule this lane polls: slot, weight, row -- looked up when the slot changes
     int32_t cur_row = 0;
-    int cur_mul = 0;
 #pragma unroll
     for (int k = 0; k < C; k++) {
       pt[k] = A::zero();
       // decoder: the coded coefficients are input -- fetched here, not on the chain
       qc[k] = (!kEnc && coded) ? cplane[(size_t)k * n_s] : 0;
     }
+    // Everything the prologue loaded has arrived before the loop starts: a value first used inside a stage body
+    // would otherwise put a vmcnt(0) there, and that wait would also be one for the poll in flight.
+#ifndef GPCC_EMU
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+#endif
     prof.loop_begin();
     while (__any(stage != 3)) {
       bool progressed = false;
@@ -955,7 +965,7 @@ raht_level_sub_kernel(LevelCtx ctx)
       // ---- (X) awaited children of blocks of this wavefront: the mailbox ----
       // (only when the mailbox has gained a child since the loop last ran: nothing else lets it consume one, and a waiting
       // iteration -- a round waits for ~100 of them -- is then the poll below and a handful of tests)
-      if (!GPCC_SUB_IDLE_FAST || done != done_seen) {
+      if (done != done_seen) {
         done_seen = done;
         uint32_t mi = stage == 0 ? (pend & inw) : 0u;
         while (__any(mi != 0)) {
@@ -969,10 +979,7 @@ raht_level_sub_kernel(LevelCtx ctx)
           const int sh = (int)((kShifts >> (3 * slot)) & 7);
           const int srcl = (int)(pg << 3) | ((slot < 9 ? t + sh : t - sh) & 7);
           if (act && ((done >> srcl) & 1)) {
-            int pwc = 0;
-#pragma unroll
-            for (int i12 = 0; i12 < 12; i12++)
-              pwc = slot == i12 ? pwc12[i12] : pwc;
+            const int pwc = GPCC_SUB_PWC(slot);
             const int mul = ext ? pwc : (pwc << kFpFrac);
 #pragma unroll
             for (int k = 0; k < C; k++)
@@ -986,154 +993,71 @@ raht_level_sub_kernel(LevelCtx ctx)
       // One granule per lane and iteration -- the lowest awaited one -- so an
       // iteration costs ONE memory round trip however many different
       // neighbours the 64 lanes wait for (polling slot after slot made it
-      // as many round trips as there were slots in use).
-      // (Skipping the poll in an iteration that has a group ready to compute -- so that a chain
-      // inside the wavefront never stalls on a memory round trip -- was measured: 7.22 / 4.17 ms
-      // against 6.98 / 3.95, arrivals from other wavefronts are what the frame waits for.)
+      // as many round trips as there were slots in use).  Its row and weight
+      // are looked up when the lane's slot changes.
+      // The poll is issued in EVERY iteration (skipping it in an iteration that has a group ready to compute
+      // was measured: 7.22 / 4.17 ms against 6.98 / 3.95, arrivals from other wavefronts are what the frame
+      // waits for), but it is only WAITED FOR here when no group can go on without its answer.  A group fed
+      // from the mailbox above -- most hops of the longest chains are hops inside a wavefront -- computes
+      // while the round trip is in flight; the answer is taken behind the stage bodies, in front of the
+      // iteration's first store (on gfx9 vmcnt counts stores too), and a group it completes runs in the
+      // next iteration.
       const uint32_t pm = stage == 0 ? (pend & ~inw) : 0u;
-#if GPCC_SUB_POLL_N > 1
-      // (experiment) the GPCC_SUB_POLL_N lowest awaited granules of a lane side by side: neighbours produced by ONE earlier
-      // round arrive together, and one granule per iteration consumes them a memory round trip apart
+      u32x4 g[C];
       if (pm) {
-        uint32_t pmm = pm;
-        int slot_[GPCC_SUB_POLL_N], pwc_[GPCC_SUB_POLL_N];
-        bool act_[GPCC_SUB_POLL_N];
-        u32x4 g[GPCC_SUB_POLL_N][C];
-#pragma unroll
-        for (int u = 0; u < GPCC_SUB_POLL_N; u++) {
-          act_[u] = pmm != 0;
-          slot_[u] = act_[u] ? __ffs(pmm) - 1 : __ffs(pm) - 1;
-          pmm &= pmm - 1;
-          int32_t row = 0;
-          pwc_[u] = 0;
-#pragma unroll
-          for (int i12 = 0; i12 < 12; i12++) {
-            if (slot_[u] == i12) {
-              row = nrow12[i12];
-              pwc_[u] = pwc12[i12];
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < C; k++)
-            g[u][k] = __builtin_amdgcn_raw_buffer_load_b128(mrsrc, (row * C + k) * 16, 0, /*sc1*/ 16);
-        }
-#pragma unroll
-        for (int u = 0; u < GPCC_SUB_POLL_N; u++) {
-          bool ok = act_[u];
-#pragma unroll
-          for (int k = 0; k < C; k++)
-            ok = ok && g[u][k].z == ctx.mtag;
-          if (ok) {
-            const int mul = ext ? pwc_[u] : (pwc_[u] << kFpFrac);
-#pragma unroll
-            for (int k = 0; k < C; k++)
-              pred[k] += A::muli(__builtin_bit_cast(VT, ((uint64_t)g[u][k].y << 32) | g[u][k].x), mul);
-            pend &= ~(1u << slot_[u]);
-          }
-        }
-      }
-#else
-      if (pm) {
-#if GPCC_SUB_POLL_RR
-        // round robin over the awaited granules: the one behind the last polled.  Polling the LOWEST awaited one until it
-        // arrives makes every other neighbour -- long there -- wait its turn behind a late one, an iteration each after it
-        // has arrived; in turn they are consumed while the late one is still out (the sums are exact: order is free)
-        const uint32_t above = pm & ~((2u << poll_last) - 1u);
-        const int slot = __ffs(above ? above : pm) - 1;
-        poll_last = slot;
-#else
         const int slot = __ffs(pm) - 1;
-#endif
-        int32_t row = 0;
-        int pwc = 0;
-        if (GPCC_SUB_IDLE_FAST && !GPCC_SUB_POLL_RR) {
-          if (slot != cur_slot) {
-            cur_slot = slot;
-#pragma unroll
-            for (int i12 = 0; i12 < 12; i12++) {
-              if (slot == i12) {
-                cur_row = nrow12[i12];
-                cur_pwc = pwc12[i12];
-              }
-            }
-          }
-          row = cur_row;
-          pwc = cur_pwc;
-        } else {
-#pragma unroll
-          for (int i12 = 0; i12 < 12; i12++) {
-            if (slot == i12) {
-              row = nrow12[i12];
-              pwc = prm->pred_weight_child[i12];
-            }
-          }
+        if (slot != cur_slot) {
+          cur_slot = slot;
+          cur_row = GPCC_SUB_NROW(slot);
+          cur_pwc = GPCC_SUB_PWC(slot);
         }
-#if GPCC_SUB_IDLE_SPIN
-        cur_mul = ext ? pwc : (pwc << kFpFrac);
-      }
-      {
-        // Nothing but an arrival from another wavefront lets this one go on -- no group waits for the zero-run state,
-        // none is ready to predict, the mailbox has been looked at: poll in place.  (The waiting iteration is what a
-        // round spends ~100 of, three wavefronts per SIMD at a time: every instruction of it is also taken from the
-        // issue slots of the wavefront that has work -- profiles/r06_idle_ab.txt.)
-        const bool spin_ok = !__any(stage == 1) && !__any(stage == 0 && !group8_any(stage == 0 && pend));
-        u32x4 g[C];
-        bool ok = false;
-        bool expired = false;
-        for (;;) {
-          if (pm) {
-#pragma unroll
-            for (int k = 0; k < C; k++)
-              g[k] = __builtin_amdgcn_raw_buffer_load_b128(mrsrc, (cur_row * C + k) * 16, 0, /*sc1*/ 16);
-            ok = true;
-#pragma unroll
-            for (int k = 0; k < C; k++)
-              ok = ok && g[k].z == ctx.mtag;
-          }
-          if (!spin_ok || __any(ok) || !__any(pm != 0))
-            break;
-          prof.idle();
-          if (++spins > (1u << 21)) {
-            expired = true;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(GPCC_SUB_SLEEP);
-        }
-        if (expired) {
-          if (lane == 0)
-            atomicExch(ctx.error, 1);  // fail loudly instead of hanging the GPU
-          break;
-        }
-        if (ok) {
-          // (a granule carries the value in the launch's arithmetic: every reader is this launch)
-#pragma unroll
-          for (int k = 0; k < C; k++)
-            pred[k] += A::muli(__builtin_bit_cast(VT, ((uint64_t)g[k].y << 32) | g[k].x), cur_mul);
-          pend &= ~(1u << cur_slot);
-        }
-      }
-#else
-        u32x4 g[C];
 #pragma unroll
         for (int k = 0; k < C; k++)
-          g[k] = __builtin_amdgcn_raw_buffer_load_b128(mrsrc, (row * C + k) * 16, 0, /*sc1*/ 16);
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < C; k++)
-          ok = ok && g[k].z == ctx.mtag;
-        if (ok) {
-          // (a granule carries the value in the launch's arithmetic: every reader is this launch)
-          const int mul = ext ? pwc : (pwc << kFpFrac);
-#pragma unroll
-          for (int k = 0; k < C; k++)
-            pred[k] += A::muli(__builtin_bit_cast(VT, ((uint64_t)g[k].y << 32) | g[k].x), mul);
-          pend &= ~(1u << slot);
-        }
+          g[k] = __builtin_amdgcn_raw_buffer_load_b128(mrsrc, (cur_row * C + k) * 16, 0, /*sc1*/ 16);
       }
+      // the answer: an arrived granule joins the prediction (it carries the value in the launch's arithmetic:
+      // every reader is this launch); true when one has
+      auto take_poll = [&]() -> bool {
+        bool ok = pm != 0;
+        if (pm) {
+#pragma unroll
+          for (int k = 0; k < C; k++) {
+#ifndef GPCC_EMU
+            // (the granule's unused fourth word stays allocated until here: a stage body that took its register
+            // for a temporary would have to wait for the load first)
+            asm volatile("" : : "v"(g[k]));
 #endif
+            ok = ok && g[k].z == ctx.mtag;
+          }
+          if (ok) {
+            const int mul = ext ? cur_pwc : (cur_pwc << kFpFrac);
+#pragma unroll
+            for (int k = 0; k < C; k++)
+              pred[k] += A::muli(__builtin_bit_cast(VT, ((uint64_t)g[k].y << 32) | g[k].x), mul);
+            pend &= ~(1u << cur_slot);
+          }
+        }
+        return ok;
+      };
+      bool blocked = group8_any(stage == 0 && pend);
+      bool poll_open = __any(stage == 0 && !blocked);  // (wave-uniform) the answer is taken behind the stage bodies
+      if (!poll_open) {
+        // a waiting iteration: nothing to do but look at the answer
+        if (__any(take_poll()))
+          blocked = group8_any(stage == 0 && pend);
+      }
+      // Where the answer is taken otherwise: ONE place that every iteration passes, in front of the iteration's
+      // first store -- behind (P) and (Z) in the lossy encoder, behind the inverse butterflies of (W) in the others.
+      // The wait is written out so that nothing of the poll is pending on any path behind it (a wait the compiler
+      // placed at the top of the next iteration would be one for this iteration's write-through stores).
+      auto take_poll_behind = [&]() {
+#ifndef GPCC_EMU
+        __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
 #endif
+        if (poll_open)
+          take_poll();
+      };
       prof.mark<0>();
-      const bool blocked = group8_any(stage == 0 && pend);
       const bool nready = stage == 0 && !blocked;
 
       if (__any(nready)) {
@@ -1171,7 +1095,12 @@ raht_level_sub_kernel(LevelCtx ctx)
 #pragma unroll
           for (int k = 0; k < C; k++) {
             const VT own = pw_[k], oth = shfl_xor_v(own, bit);
-            if (enable_pred) {
+            if constexpr (A::kF64) {
+              // one straight line for the whole group: the right lane's difference is a sum with the partner
+              // negated (mulc(-x, c) == -mulc(x, c) exactly), and the lanes that keep or swap take selects
+              const VT bf = A::mulc(own, ca[st]) + A::mulc(left ? oth : -oth, cb[st]);
+              pw_[k] = !enable_pred ? own : (both ? bf : (swap ? oth : own));
+            } else if (enable_pred) {
               if (both) {
                 if (haar) {
                   if constexpr (!A::kF64) {
@@ -1233,8 +1162,7 @@ raht_level_sub_kernel(LevelCtx ctx)
               if (sum_coeff == 0 && !any) {
                 d = kDescZero;
               } else {
-                const int64_t l0 = qr[0].step;
-                d = rdoq_threshold(dist2, l0 * l0 * (C == 1 ? 25 : 35), rate_coeff, (uint32_t)n_s);
+                d = rdoq_threshold_recip(dist2, rd_lambda, rd_inv_lambda, rate_coeff, (uint32_t)n_s);
                 if (sum_coeff == 0)
                   d |= kDescZero;
               }
@@ -1434,6 +1362,7 @@ raht_level_sub_kernel(LevelCtx ctx)
               break;
           }
         }
+        take_poll_behind();
         can = stage == 1 && zs == 2;
         if (can && t == 0) {
           // what this block does to L: its last reset (or the known state passing through), or
@@ -1448,14 +1377,14 @@ raht_level_sub_kernel(LevelCtx ctx)
       }
 
       prof.mark<2>();
+      VT pw_[C];
+#pragma unroll
+      for (int k = 0; k < C; k++)
+        pw_[k] = pt[k];
       if (__any(can)) {
         progressed = true;
         // ---- (W) coefficients, DC, inverse transform, commit ---------------
         prof.template enter<1>();
-        VT pw_[C];
-#pragma unroll
-        for (int k = 0; k < C; k++)
-          pw_[k] = pt[k];
         bool zero_me = false;
         if (kLossy)
           zero_me = __shfl((int)zero_r, gbase | (crank & 7)) != 0 && coded;
@@ -1489,7 +1418,10 @@ raht_level_sub_kernel(LevelCtx ctx)
 #pragma unroll
           for (int k = 0; k < C; k++) {
             const VT own = pw_[k], oth = shfl_xor_v(own, bit);
-            if (both) {
+            if constexpr (A::kF64) {
+              const VT bf = A::mulc(own, ca[st]) + A::mulc(left ? -oth : oth, cb[st]);
+              pw_[k] = both ? bf : (swap ? oth : own);
+            } else if (both) {
               if (haar) {
                 if constexpr (!A::kF64) {
                   const int64_t lf = left ? own : oth, hf = left ? oth : own;
@@ -1506,6 +1438,10 @@ raht_level_sub_kernel(LevelCtx ctx)
           }
         }
         prof.template sub<2>();
+      }
+      if (!kLossy)
+        take_poll_behind();
+      if (__any(can)) {
         // children of the committing groups: the value later launches read
         // (plain store) and the mailbox granule later blocks of THIS launch
         // poll (one 16-byte write-through store: value + tag, untorn)
@@ -1575,6 +1511,8 @@ raht_level_sub_kernel(LevelCtx ctx)
   // ArithI64 (host tier) or reports GPCC_ERR_RANGE (device tier)
   if (A::kF64 && __any(!in_range) && lane == 0)
     atomicCAS(ctx.error, 0, 3);
+#undef GPCC_SUB_NROW
+#undef GPCC_SUB_PWC
 }
 
 }  // namespace gpcc

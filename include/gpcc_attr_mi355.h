@@ -286,8 +286,9 @@ typedef struct gpcc_lift_params {
   int32_t fixed_point_qp_offset;
   /* AttributeParameterSet::scalable_lifting_enabled_flag: the quantisation
    * weight of a predictor is then a function of its level of detail alone
-   * (computeQuantizationWeightsScalable, PCCTMC3Common.h:858-891, whole
-   * slices: minGeomNodeSizeLog2 = 0) */
+   * (computeQuantizationWeightsScalable, PCCTMC3Common.h:858-891; of a whole
+   * slice here, the gpcc_*_partial entries take minGeomNodeSizeLog2 and the
+   * slice's point count as arguments) */
   int32_t scalable_lifting_enabled_flag;
   /* QP regions of the slice (AttributeBrickHeader::qpRegions -> QpSet::regions,
    * tmc3/quantization.cpp:100-117), for the entries that build the LoD structure themselves
@@ -332,6 +333,23 @@ int gpcc_lift_inverse(
   const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off,
   int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs);
 
+/* decodeColorsLift / decodeReflectancesLift over the predictors of a PARTIALLY decoded
+ * scalable-lifting slice (minGeomNodeSizeLog2 = m > 0, AttributeDecoder.cpp:692-698, 791-797
+ * -> computeQuantizationWeightsScalable, PCCTMC3Common.h:858-891): the quantisation weight of
+ * a level is geom_num_points / (points up to and including it) with the slice's FULL point
+ * count geom_num_points = geom_num_points_minus1 + 1 >= n, and the finest level gets no unit
+ * weight (:884).  Everything else is gpcc_lift_inverse over the n predictors given (as built
+ * by gpcc_lod_build_partial): coeffs [n][c] are the first n entries of the slice's
+ * coefficient sequence, lcp_coeffs are read by the partial structure's own LoD index.
+ *   min_geom_node_size_log2 in [0, 20]; > 0 needs params->scalable_lifting_enabled_flag
+ *   (GPCC_ERR_INVALID_ARG otherwise).  With 0 and geom_num_points = n: gpcc_lift_inverse. */
+int gpcc_lift_inverse_partial(
+  gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n, int32_t c,
+  int32_t min_geom_node_size_log2, int32_t geom_num_points,
+  const int32_t* neigh_count, const int32_t* neigh_index,
+  const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off,
+  int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs);
+
 /* Flattened LoD-generation parameters: the AttributeParameterSet fields
  * buildPredictorsFast reads (hls.h:782-876) plus
  * AttributeBrickHeader::attr_dist2_delta: the parameter block of
@@ -372,8 +390,8 @@ typedef struct gpcc_lod_params {
  * geometry coder hands over; then neither changes the result.  Points in any
  * other order with those flags and inter prediction return
  * GPCC_ERR_UNSUPPORTED (the shim keeps them on the reference path).
- * scalable_lifting_enabled_flag (whole slices: minGeomNodeSizeLog2 = 0, no
- * points skipped by a partial decode) builds the structure of
+ * scalable_lifting_enabled_flag (of a whole slice: minGeomNodeSizeLog2 = 0, no
+ * points skipped -- gpcc_lod_build_partial is the partial decode) builds the structure of
  * PCCTMC3Common.h:2377-2448: always 21 levels, octree sub-sampling by LoD
  * index, node-corner positions in the search, neighbours beyond
  * max_neigh_range_minus1 dropped, the finer layers searched again while a new
@@ -385,6 +403,25 @@ int gpcc_lod_build(
   gpcc_ctx* ctx, const gpcc_lod_params* params, const int32_t* xyz, int32_t n,
   int32_t* neigh_count, int32_t* neigh_index, int32_t* neigh_weight,
   int32_t* indexes, int32_t* num_points_in_lod, int32_t* num_lods);
+
+/* AttributeLods::generate of a PARTIALLY decoded slice (spatial scalability,
+ * AttributeCommon.cpp:44-72 with minGeomNodeSizeLog2 = m > 0; buildPredictorsFast,
+ * PCCTMC3Common.h:2404-2443): the geometry decoder stopped the octree m levels early
+ * (tmc3/decoder.cpp:697-738, geometry_octree_decoder.cpp:2244-2280), xyz [n][3] is the
+ * coarser cloud it left (n = P points) and geom_num_points = geom_num_points_minus1 + 1
+ * >= n is what the slice header counts.  The level loop runs from LoD m to 20 -- node size,
+ * walk direction, corner mask, cell shift and prune distance by the absolute level,
+ * num_points_in_lod counted from m -- and the points the decoder never saw count among the
+ * finer layers of the "search again" rule (:2424-2425).  Outputs as gpcc_lod_build.
+ *   min_geom_node_size_log2 in [0, 20]; > 0 needs scalable_lifting_enabled_flag and
+ *   attr_encoding 2 (GPCC_ERR_INVALID_ARG otherwise; the predicting transform returns
+ *   GPCC_ERR_UNSUPPORTED: the reference's drivers of it take no m).
+ *   With min_geom_node_size_log2 = 0 and geom_num_points = n: exactly gpcc_lod_build. */
+int gpcc_lod_build_partial(
+  gpcc_ctx* ctx, const gpcc_lod_params* params, const int32_t* xyz, int32_t n,
+  int32_t min_geom_node_size_log2, int32_t geom_num_points, int32_t* neigh_count,
+  int32_t* neigh_index, int32_t* neigh_weight, int32_t* indexes,
+  int32_t* num_points_in_lod, int32_t* num_lods);
 
 /* AttributeLods::generate with attribute INTER prediction
  * (AttributeInterPredParams::enableAttrInterPred; buildPredictorsFast with
@@ -509,6 +546,19 @@ int gpcc_lift_decode_attr(
   const int32_t* xyz, int32_t* attrs, const int32_t* coeffs,
   const int8_t* lcp_coeffs, int32_t* indexes, int32_t n, int32_t c);
 
+/* gpcc_lift_decode_attr of a PARTIALLY decoded scalable-lifting slice
+ * (AttributeDecoder::decode with minGeomNodeSizeLog2 = m > 0, AttributeDecoder.cpp:292-296,
+ * 678-857): gpcc_lod_build_partial + gpcc_lift_inverse_partial in one call, the structure
+ * never leaves the device.  xyz [n][3] is the coarser cloud, coeffs [n][c] the FIRST n
+ * entries of the slice's coefficient sequence (the entropy decoder stops there), lcp_coeffs
+ * the brick header's, read by the partial structure's own LoD index.  Arguments and checks
+ * as gpcc_lod_build_partial; decode only (the encoder always codes whole slices). */
+int gpcc_lift_decode_attr_partial(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift,
+  const int32_t* xyz, int32_t* attrs, const int32_t* coeffs,
+  const int8_t* lcp_coeffs, int32_t* indexes, int32_t n, int32_t c,
+  int32_t min_geom_node_size_log2, int32_t geom_num_points);
+
 /* ------------------------------------------------------------------ */
 /* predicting transform                                                  */
 
@@ -535,7 +585,7 @@ typedef struct gpcc_pred_params {
                                           * beyond it are zero */
   int32_t scalable_lifting_enabled_flag; /* quantisation weights by level of detail
                                           * (computeQuantizationWeightsScalable,
-                                          * PCCTMC3Common.h:858-891; whole slices) instead
+                                          * PCCTMC3Common.h:858-891) instead
                                           * of quant_neigh_weight */
   /* QP regions of the slice (AttributeBrickHeader::qpRegions -> QpSet::regions,
    * tmc3/quantization.cpp:100-117), for the entries that build the LoD structure themselves
@@ -743,6 +793,16 @@ int gpcc_dev_lift_decode_attr(
   gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift,
   int32_t num_slices, const int64_t* offsets, const void* d_xyz, void* d_attrs,
   const void* d_coeffs, const int8_t* lcp_coeffs, void* d_indexes, int32_t c);
+
+/* gpcc_dev_lift_decode_attr_partial: gpcc_lift_decode_attr_partial for every slice of a
+ * batch resident in HBM.  One min_geom_node_size_log2 for the call (a decoder stops every
+ * slice at the same node size); geom_num_points is a HOST array [num_slices], the full
+ * point count of each slice (>= its offsets[s + 1] - offsets[s]). */
+int gpcc_dev_lift_decode_attr_partial(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift,
+  int32_t num_slices, const int64_t* offsets, const void* d_xyz, void* d_attrs,
+  const void* d_coeffs, const int8_t* lcp_coeffs, void* d_indexes, int32_t c,
+  int32_t min_geom_node_size_log2, const int32_t* geom_num_points);
 
 /* gpcc_dev_pred_encode_attr / _decode_attr: gpcc_pred_encode_attr /
  * gpcc_pred_decode_attr for every slice of a batch resident in HBM (slices

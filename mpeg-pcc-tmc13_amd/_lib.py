@@ -29,6 +29,8 @@ ABI_SYMBOLS = [
     "gpcc_multi_lift_encode_attr", "gpcc_multi_lift_decode_attr", "gpcc_multi_pred_encode_attr", "gpcc_multi_pred_decode_attr",
     "gpcc_pred_forward", "gpcc_pred_inverse", "gpcc_pred_encode_attr", "gpcc_pred_decode_attr",
     "gpcc_dev_pred_encode_attr", "gpcc_dev_pred_decode_attr",
+    "gpcc_lod_build_partial", "gpcc_lift_inverse_partial", "gpcc_lift_decode_attr_partial",
+    "gpcc_dev_lift_decode_attr_partial",
     "gpcc_ctx_reserve",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_guard_selftest",
@@ -130,6 +132,13 @@ def load():
     lib.gpcc_dev_lod_build.argtypes = [vp, C.POINTER(LodParams), i32, i64p, vp, vp, vp, vp, vp, vp, vp]
     for name in ("gpcc_dev_lift_encode_attr", "gpcc_dev_lift_decode_attr"):
         getattr(lib, name).argtypes = [vp, C.POINTER(LodParams), vp, i32, i64p, vp, vp, vp, vp, vp, i32]
+    # the partial (spatially scalable) decode: minGeomNodeSizeLog2 and the slice's full point count as arguments
+    lib.gpcc_lod_build_partial.argtypes = [vp, C.POINTER(LodParams), vp, i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]
+    lib.gpcc_lift_inverse_partial.argtypes = [vp, C.POINTER(LiftParams), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gpcc_lift_decode_attr_partial.argtypes = [vp, C.POINTER(LodParams), C.POINTER(LiftParams), vp, vp, vp, vp, vp,
+                                                  i32, i32, i32, i32]
+    lib.gpcc_dev_lift_decode_attr_partial.argtypes = [vp, C.POINTER(LodParams), vp, i32, i64p, vp, vp, vp, vp, vp, i32,
+                                                      i32, vp]
     lib.gpcc_multi_create.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
     lib.gpcc_multi_destroy.argtypes = [vp]
     lib.gpcc_multi_destroy.restype = None

@@ -1796,6 +1796,39 @@ check_lift_params(const gpcc_lift_params* p, int n, int c)
   return GPCC_OK;
 }
 
+// Partial (spatially scalable) decode of a scalable-lifting slice: the geometry decoder
+// stopped `first_level` octree levels early (minGeomNodeSizeLog2) and the n points of the call
+// stand for the geom_num_points the slice header counts (geom_num_points_minus1 + 1).
+struct PartialDecode {
+  int32_t first_level;
+  int64_t geom_num_points;
+};
+
+// `scalable` / `attr_encoding` / `inter`: of the slice the call decodes
+int
+check_partial(const PartialDecode& pd, int64_t n, bool scalable, int attr_encoding, bool inter)
+{
+  if (pd.first_level < 0 || pd.first_level > 20)
+    return fail(GPCC_ERR_INVALID_ARG, "min_geom_node_size_log2 outside [0, 20]");
+  if (pd.geom_num_points < n || pd.geom_num_points > INT32_MAX)
+    return fail(GPCC_ERR_INVALID_ARG, "geom_num_points below the number of points of the call");
+  if (pd.first_level > 0) {
+    if (scalable && attr_encoding == 1)
+      return fail(
+        GPCC_ERR_UNSUPPORTED,
+        "a partial decode (min_geom_node_size_log2 > 0) of the predicting transform stays on the reference CPU path");
+    if (!scalable || attr_encoding != 2)
+      return fail(
+        GPCC_ERR_INVALID_ARG,
+        "min_geom_node_size_log2 > 0 needs scalable_lifting_enabled_flag and the lifting transform");
+    if (inter)
+      return fail(
+        GPCC_ERR_UNSUPPORTED,
+        "a partial decode (min_geom_node_size_log2 > 0) with inter prediction stays on the reference CPU path");
+  }
+  return GPCC_OK;
+}
+
 // Attribute inter prediction (n_frame > 0): the working arrays get n_frame entries
 // BEHIND the n predictors.  a[n + r] holds the reference frame's attribute r in fixed
 // point (h_frame, host memory, [n_frame][C]) and the caller has pointed every neighbour
@@ -1808,7 +1841,7 @@ int
 launch_lift(
   gpcc_ctx* ctx, bool encoder, const gpcc_lift_params* p, int n,
   const LiftDev& d, int8_t* d_lcp_io, char* scratch, int n_frame = 0,
-  const int64_t* h_frame = nullptr)
+  const int64_t* h_frame = nullptr, const PartialDecode* partial = nullptr)
 {
   hipStream_t st = ctx->stream;
   LiftCtx cx{};
@@ -1896,7 +1929,13 @@ launch_lift(
       t.num_lods = p->num_lods;
       for (int l = 0; l < p->num_lods; l++)
         t.npl[l] = p->num_points_in_lod[l];
-      quant_weights_scalable_kernel<<<grid(n), 256, 0, st>>>(n, t, cx.qw);
+      // (AttributeDecoder.cpp:692-698, 791-797: the slice's point count, and no unit weight for
+      // the finest level of a partial decode)
+      if (partial && (partial->first_level > 0 || partial->geom_num_points != n))
+        quant_weights_scalable_partial_kernel<<<grid(n), 256, 0, st>>>(
+          n, (long long)partial->geom_num_points, partial->first_level == 0, t, cx.qw);
+      else
+        quant_weights_scalable_kernel<<<grid(n), 256, 0, st>>>(n, t, cx.qw);
     } else
       for (int l = p->num_lods - 1; l >= 1; l--)
         if (npl[l] > npl[l - 1])
@@ -1957,13 +1996,20 @@ host_lift(
   int32_t* coeffs, int8_t* lcp,
   // attribute inter prediction (null: none): inter_ref [n][3] marks the neighbours that live in
   // the reference frame (ni is then a point index there), attrs_ref [n_frame][c] its attributes
-  const int32_t* inter_ref = nullptr, const int32_t* attrs_ref = nullptr, int n_frame = 0)
+  const int32_t* inter_ref = nullptr, const int32_t* attrs_ref = nullptr, int n_frame = 0,
+  const PartialDecode* partial = nullptr)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
   int rcode = check_lift_params(p, n, c);
   if (rcode)
     return rcode;
+  if (partial) {
+    // (this entry IS the lifting transform: attr_encoding 2)
+    rcode = check_partial(*partial, n, p->scalable_lifting_enabled_flag != 0, 2, inter_ref != nullptr);
+    if (rcode)
+      return rcode;
+  }
   if (!nc || !ni || !nw || !indexes || !attrs || !coeffs)
     return fail(GPCC_ERR_INVALID_ARG, "null buffer");
   const bool lcp_on = c == 3 && p->last_component_prediction_enabled_flag;
@@ -2052,9 +2098,9 @@ host_lift(
       HIP_TRY(hipMemcpyAsync(d_lcp, lcp, GPCC_MAX_LODS, hipMemcpyHostToDevice, st));
   }
   switch (c) {
-  case 1: rcode = launch_lift<1>(ctx, encoder, p, n, d, d_lcp, scratch, n_frame, a_frame.data()); break;
-  case 2: rcode = launch_lift<2>(ctx, encoder, p, n, d, d_lcp, scratch); break;
-  default: rcode = launch_lift<3>(ctx, encoder, p, n, d, d_lcp, scratch); break;
+  case 1: rcode = launch_lift<1>(ctx, encoder, p, n, d, d_lcp, scratch, n_frame, a_frame.data(), partial); break;
+  case 2: rcode = launch_lift<2>(ctx, encoder, p, n, d, d_lcp, scratch, 0, nullptr, partial); break;
+  default: rcode = launch_lift<3>(ctx, encoder, p, n, d, d_lcp, scratch, 0, nullptr, partial); break;
   }
   if (rcode)
     return rcode;
@@ -3195,6 +3241,19 @@ gpcc_lift_inverse_impl(
 }
 
 static int
+gpcc_lift_inverse_partial_impl(
+  gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n, int32_t c, int32_t min_geom_node_size_log2,
+  int32_t geom_num_points, const int32_t* neigh_count, const int32_t* neigh_index,
+  const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off, int32_t* attrs,
+  const int32_t* coeffs, const int8_t* lcp_coeffs)
+{
+  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
+  return host_lift(
+    ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs,
+    const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs), nullptr, nullptr, 0, &pd);
+}
+
+static int
 gpcc_lod_compute_weights_impl(
   gpcc_ctx* ctx, int32_t n, int32_t* neigh_count, const uint64_t* dist2,
   int32_t* neigh_weight)
@@ -3287,7 +3346,7 @@ int
 lod_build_core(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n,
   size_t extra_bytes, LodDeviceOut* out, bool xyz_on_device = false,
-  const LodInterFrame* frame = nullptr)
+  const LodInterFrame* frame = nullptr, const PartialDecode* partial = nullptr)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
@@ -3295,6 +3354,11 @@ lod_build_core(
     return fail(GPCC_ERR_INVALID_ARG, "null buffer or n <= 0");
   if (n > kMaxPoints)
     return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per call");
+  if (partial) {
+    int rp = check_partial(*partial, n, lp->scalable_lifting_enabled_flag != 0, lp->attr_encoding, frame != nullptr);
+    if (rp)
+      return rp;
+  }
   if (frame) {
     if (!frame->xyz || frame->n <= 0 || frame->n > kMaxPoints || frame->search_range < 0 || xyz_on_device)
       return fail(GPCC_ERR_INVALID_ARG, "reference frame: null, empty, too large or a negative search range");
@@ -3567,7 +3631,9 @@ lod_build_core(
       w.pt2pred = d_pt2pred;
       w.indexes = d_indexes;
       Timer tm(ctx, "lod_scalable_levels");
-      HIP_TRY(lod_scalable_levels(lp, w, st, &npl, &scan_epoch));
+      HIP_TRY(lod_scalable_levels(
+        lp, w, st, &npl, &scan_epoch, partial ? partial->first_level : 0,
+        partial ? partial->geom_num_points - n : 0));
       n_in = 0;  // the loop below has nothing left to do
     }
     for (int lod = 0; n_in > 0 && lod < max_levels; lod++) {
@@ -3773,12 +3839,13 @@ static int
 gpcc_lod_build_impl(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n,
   int32_t* neigh_count, int32_t* neigh_index, int32_t* neigh_weight,
-  int32_t* indexes, int32_t* num_points_in_lod, int32_t* num_lods)
+  int32_t* indexes, int32_t* num_points_in_lod, int32_t* num_lods,
+  const PartialDecode* partial = nullptr)
 {
   if (!neigh_count || !neigh_index || !neigh_weight || !indexes || !num_points_in_lod || !num_lods)
     return fail(GPCC_ERR_INVALID_ARG, "null output buffer");
   LodDeviceOut o;
-  int r = lod_build_core(ctx, lp, xyz, n, 0, &o);
+  int r = lod_build_core(ctx, lp, xyz, n, 0, &o, false, nullptr, partial);
   if (r)
     return r;
   hipStream_t st = ctx->stream;
@@ -3915,7 +3982,7 @@ static int
 lift_attr_driver(
   gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, gpcc_lift_params* lift,
   const int32_t* xyz, int32_t* attrs, int32_t* coeffs, int8_t* lcp, int32_t* indexes,
-  int32_t n, int32_t c)
+  int32_t n, int32_t c, const PartialDecode* partial = nullptr)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
@@ -3928,7 +3995,7 @@ lift_attr_driver(
   const size_t extra = ((N * c * sizeof(int32_t) + 255) & ~size_t(255)) * 2 + 256
     + lift_scratch_bytes(n > 0 ? n : 1, c) + 1024 + N * 8 + 256;
   LodDeviceOut o;
-  int r = lod_build_core(ctx, lod, xyz, n, extra, &o);
+  int r = lod_build_core(ctx, lod, xyz, n, extra, &o, false, nullptr, partial);
   if (r)
     return r;
   lift->scalable_lifting_enabled_flag = lod->scalable_lifting_enabled_flag != 0;
@@ -3963,9 +4030,9 @@ lift_attr_driver(
       HIP_TRY(hipMemcpyAsync(d_lcp, lcp, GPCC_MAX_LODS, hipMemcpyHostToDevice, st));
   }
   switch (c) {
-  case 1: r = launch_lift<1>(ctx, encoder, lift, n, d, d_lcp, scratch); break;
-  case 2: r = launch_lift<2>(ctx, encoder, lift, n, d, d_lcp, scratch); break;
-  default: r = launch_lift<3>(ctx, encoder, lift, n, d, d_lcp, scratch); break;
+  case 1: r = launch_lift<1>(ctx, encoder, lift, n, d, d_lcp, scratch, 0, nullptr, partial); break;
+  case 2: r = launch_lift<2>(ctx, encoder, lift, n, d, d_lcp, scratch, 0, nullptr, partial); break;
+  default: r = launch_lift<3>(ctx, encoder, lift, n, d, d_lcp, scratch, 0, nullptr, partial); break;
   }
   if (r)
     return r;
@@ -4002,6 +4069,18 @@ gpcc_lift_decode_attr_impl(
   return lift_attr_driver(
     ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs),
     const_cast<int8_t*>(lcp_coeffs), indexes, n, c);
+}
+
+static int
+gpcc_lift_decode_attr_partial_impl(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
+  int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs, int32_t* indexes, int32_t n,
+  int32_t c, int32_t min_geom_node_size_log2, int32_t geom_num_points)
+{
+  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
+  return lift_attr_driver(
+    ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs),
+    const_cast<int8_t*>(lcp_coeffs), indexes, n, c, &pd);
 }
 
 namespace {
@@ -4612,6 +4691,55 @@ gpcc_lod_build(
 }
 
 int
+gpcc_lod_build_partial(
+  gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n,
+  int32_t min_geom_node_size_log2, int32_t geom_num_points, int32_t* neigh_count,
+  int32_t* neigh_index, int32_t* neigh_weight, int32_t* indexes, int32_t* num_points_in_lod,
+  int32_t* num_lods)
+{
+  // (the two scalars are checked first: they need neither the context nor a buffer)
+  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
+  if (lp && n > 0) {
+    const int rc = check_partial(pd, n, lp->scalable_lifting_enabled_flag != 0, lp->attr_encoding, false);
+    if (rc)
+      return counted(ctx, rc, n);
+  }
+  return counted(ctx, gpcc_lod_build_impl(ctx, lp, xyz, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods, &pd), n);
+}
+
+int
+gpcc_lift_inverse_partial(
+  gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n, int32_t c,
+  int32_t min_geom_node_size_log2, int32_t geom_num_points, const int32_t* neigh_count,
+  const int32_t* neigh_index, const int32_t* neigh_weight, const int32_t* indexes,
+  const int32_t* qp_off, int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs)
+{
+  if (params && n > 0) {
+    const int rc = check_partial(
+      PartialDecode{min_geom_node_size_log2, geom_num_points}, n, params->scalable_lifting_enabled_flag != 0, 2, false);
+    if (rc)
+      return counted(ctx, rc, n);
+  }
+  return counted(ctx, gpcc_lift_inverse_partial_impl(ctx, params, n, c, min_geom_node_size_log2, geom_num_points, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, coeffs, lcp_coeffs), n);
+}
+
+int
+gpcc_lift_decode_attr_partial(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
+  int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs, int32_t* indexes, int32_t n,
+  int32_t c, int32_t min_geom_node_size_log2, int32_t geom_num_points)
+{
+  if (lod && n > 0) {
+    const int rc = check_partial(
+      PartialDecode{min_geom_node_size_log2, geom_num_points}, n, lod->scalable_lifting_enabled_flag != 0,
+      lod->attr_encoding, false);
+    if (rc)
+      return counted(ctx, rc, n);
+  }
+  return counted(ctx, gpcc_lift_decode_attr_partial_impl(ctx, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c, min_geom_node_size_log2, geom_num_points), n);
+}
+
+int
 gpcc_lod_build_inter(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n, const int32_t* xyz_ref,
   int32_t n_ref, int32_t search_range, int32_t frame_distance, int32_t* neigh_count,
@@ -4910,13 +5038,20 @@ int
 dev_lift_attr(
   gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, gpcc_lift_params* lift,
   int32_t num_slices, const int64_t* offsets, const int32_t* d_xyz, int32_t* d_attrs,
-  int32_t* d_coeffs, int8_t* lcp, int32_t* d_indexes, int32_t c)
+  int32_t* d_coeffs, int8_t* lcp, int32_t* d_indexes, int32_t c,
+  // partial decode (null: whole slices): one first level for the batch, the slices' full point counts
+  const int32_t* min_geom_node_size_log2 = nullptr, const int32_t* geom_num_points = nullptr)
 {
   int r = check_slices(ctx, num_slices, offsets);
   if (r)
     return r;
   if (!lift || !d_xyz || !d_attrs || !d_coeffs || c < 1 || c > 3)
     return fail(GPCC_ERR_INVALID_ARG, "null buffer or attribute count not 1..3");
+  if (min_geom_node_size_log2) {
+    if (!lod || !geom_num_points)
+      return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+    // (the scalars themselves: checked by the entry, and again per slice by lod_build_core)
+  }
   for (int s = 0; s < num_slices; s++)
     if (c == 3 && lift[s].last_component_prediction_enabled_flag && !lcp)
       return fail(GPCC_ERR_INVALID_ARG, "lcp_coeffs is null");
@@ -4929,7 +5064,11 @@ dev_lift_attr(
     const int32_t n = (int32_t)N;
     const size_t extra = 512 + lift_scratch_bytes(n, c) + 1024 + N * 8 + 256;
     LodDeviceOut o;
-    r = lod_build_core(lane, lod, d_xyz + 3 * b, n, extra, &o, true);
+    PartialDecode pd{0, n};
+    if (min_geom_node_size_log2)
+      pd = PartialDecode{*min_geom_node_size_log2, geom_num_points[s]};
+    const PartialDecode* partial = min_geom_node_size_log2 ? &pd : nullptr;
+    r = lod_build_core(lane, lod, d_xyz + 3 * b, n, extra, &o, true, nullptr, partial);
     if (r)
       return r;
     lf->scalable_lifting_enabled_flag = lod->scalable_lifting_enabled_flag != 0;
@@ -4959,9 +5098,9 @@ dev_lift_attr(
     if (!encoder && lcp_on)
       HIP_TRY(hipMemcpyAsync(d_lcp, h_lcp, GPCC_MAX_LODS, hipMemcpyHostToDevice, st));
     switch (c) {
-    case 1: r = launch_lift<1>(lane, encoder, lf, n, d, d_lcp, scratch); break;
-    case 2: r = launch_lift<2>(lane, encoder, lf, n, d, d_lcp, scratch); break;
-    default: r = launch_lift<3>(lane, encoder, lf, n, d, d_lcp, scratch); break;
+    case 1: r = launch_lift<1>(lane, encoder, lf, n, d, d_lcp, scratch, 0, nullptr, partial); break;
+    case 2: r = launch_lift<2>(lane, encoder, lf, n, d, d_lcp, scratch, 0, nullptr, partial); break;
+    default: r = launch_lift<3>(lane, encoder, lf, n, d, d_lcp, scratch, 0, nullptr, partial); break;
     }
     if (r)
       return r;
@@ -5089,6 +5228,31 @@ gpcc_dev_lift_decode_attr(
       (int32_t*)const_cast<void*>(d_coeffs), const_cast<int8_t*>(lcp_coeffs),
       (int32_t*)d_indexes, c),
     offsets && num_slices > 0 ? offsets[num_slices] : 0);
+}
+
+int
+gpcc_dev_lift_decode_attr_partial(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, int32_t num_slices,
+  const int64_t* offsets, const void* d_xyz, void* d_attrs, const void* d_coeffs,
+  const int8_t* lcp_coeffs, void* d_indexes, int32_t c, int32_t min_geom_node_size_log2,
+  const int32_t* geom_num_points)
+{
+  const int64_t total = offsets && num_slices > 0 ? offsets[num_slices] : 0;
+  if (lod && offsets && geom_num_points)
+    for (int s = 0; s < num_slices; s++) {
+      const int rc = check_partial(
+        PartialDecode{min_geom_node_size_log2, geom_num_points[s]}, offsets[s + 1] - offsets[s],
+        lod->scalable_lifting_enabled_flag != 0, lod->attr_encoding, false);
+      if (rc)
+        return counted(ctx, rc, total);
+    }
+  return counted(
+    ctx,
+    dev_lift_attr(
+      ctx, false, lod, lift, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)const_cast<void*>(d_coeffs), const_cast<int8_t*>(lcp_coeffs),
+      (int32_t*)d_indexes, c, &min_geom_node_size_log2, geom_num_points),
+    total);
 }
 
 int

@@ -183,7 +183,7 @@ lift_quant_weights_kernel(LiftCtx cx, int start, int end)
   }
 }
 
-// computeQuantizationWeightsScalable (PCCTMC3Common.h:858-891), whole slices:
+// computeQuantizationWeightsScalable (PCCTMC3Common.h:858-891) of a whole slice:
 // numPoints / (points up to and including the predictor's level), the finest
 // level 1.  Shared by the lifting and the predicting transform.
 struct LodSizes {
@@ -199,6 +199,24 @@ quant_weights_scalable_kernel(int n, LodSizes t, unsigned long long* qw)
     while (l < t.num_lods - 1 && t.npl[l] <= i)
       l++;
     qw[i] = l == t.num_lods - 1 ? 256ull : (unsigned long long)(n / t.npl[l]) << 8;
+  }
+}
+
+// The same for a partially decoded slice (minGeomNodeSizeLog2 > 0): the numerator
+// is the slice's full point count geom_num_points_minus1 + 1, not the n points
+// the decoder holds, and the finest level is a level like the others (:884;
+// `finest_unit`: minGeomNodeSizeLog2 == 0, it keeps weight 1).
+__global__ __launch_bounds__(256) void
+quant_weights_scalable_partial_kernel(
+  int n, long long geom_num_points, int finest_unit, LodSizes t, unsigned long long* qw)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    int l = 0;
+    while (l < t.num_lods - 1 && t.npl[l] <= i)
+      l++;
+    qw[i] = finest_unit && l == t.num_lods - 1
+      ? 256ull
+      : (unsigned long long)(geom_num_points / t.npl[l]) << 8;
   }
 }
 

@@ -1,11 +1,14 @@
 // lod_scalable.hpp -- the level loop of the LoD build under
 // aps.scalable_lifting_enabled_flag (buildPredictorsFast,
 // tmc3/PCCTMC3Common.h:2300-2469 with the scalable branches :1174-1176,
-// :1232-1236, :1918-1939, :2230-2235, :2377-2448; whole slices:
-// minGeomNodeSizeLog2 = 0, no skipped points).
+// :1232-1236, :1918-1939, :2230-2235, :2377-2448), for whole slices and for
+// the partial decode (minGeomNodeSizeLog2 = m > 0: the octree stopped m levels
+// early, the cloud holds fewer points than the slice header counts).
 //
 // What changes against the level loop of lod_build_core (gpcc_attr_mi355.hip):
-//   * always 21 levels (AttributeParameterSet::maxNumDetailLevels, hls.h:835-839);
+//   * levels m .. 20 (AttributeParameterSet::maxNumDetailLevels, hls.h:835-839):
+//     node size, walk direction, corner mask, cell shift and prune distance
+//     take the absolute level, the entries of `npl` count from m;
 //   * sub-sampling is the octree one (lod_centroid_* kernels): node size = LoD
 //     index, every node is a group, the walk direction alternates;
 //   * the search of LoD l sees all positions at the corner of their node of
@@ -13,7 +16,8 @@
 //     neighbours beyond max_neigh_range (lod_nn_search_kernel<true>);
 //   * while a new refinement layer is larger than all finer layers together the
 //     finer layers are searched AGAIN against the new retained set
-//     ("concatenateLayers").  A predictor's slot depends on its position in the
+//     ("concatenateLayers"; the points the partial decode never saw count among
+//     the finer ones).  A predictor's slot depends on its position in the
 //     coding order only, so a repeated search simply overwrites its results.
 //
 // Launches are written with hipLaunchKernelGGL and the HIP runtime calls are
@@ -69,11 +73,13 @@ lod_grid(int64_t items, int per_block)
 
 // -> cumulative sizes in `npl` as the reference pushes them (n first, then the
 // retained count of every level that retains); *scan_epoch is the partition
-// kernel's epoch counter of the build
+// kernel's epoch counter of the build.  Partial decode: `first_level` is
+// minGeomNodeSizeLog2 (0..20, checked by the caller) and `skipped` >= 0 the
+// slice's points that the cloud lacks (geom_num_points_minus1 + 1 - n).
 inline hipError_t
 lod_scalable_levels(
   const gpcc_lod_params* lp, const LodWork& w, hipStream_t st, std::vector<int32_t>* npl,
-  int* scan_epoch)
+  int* scan_epoch, int first_level = 0, int64_t skipped = 0)
 {
   constexpr int kLevels = 21;
   const int n = w.n;
@@ -167,7 +173,7 @@ lod_scalable_levels(
   int32_t* d_ret = w.list_b;
   int n_in = n, n_idx = 0;
   bool concatenate = true;
-  for (int lod = 0; n_in > 0 && lod < kLevels; lod++) {
+  for (int lod = first_level; n_in > 0 && lod < kLevels; lod++) {
     const int start = n_idx;
     int n_ret = 0, n_ref = 0;
     if (lod == kLevels - 1 || n_in == 1) {
@@ -215,11 +221,12 @@ lod_scalable_levels(
     n_idx += n_ref;
 
     if (concatenate && n_ref > 0) {
-      if (n_ref <= start)
+      if (n_ref <= start + skipped)
         concatenate = false;
       else
-        for (int l = 0; l < lod; l++)
-          GPCC_LODS_TRY(search(l, n - (*npl)[l], n - (*npl)[l + 1], d_ret, n_ret));
+        for (int l = 0; l < lod - first_level; l++)
+          GPCC_LODS_TRY(
+            search(first_level + l, n - (*npl)[l], n - (*npl)[l + 1], d_ret, n_ret));
     }
     GPCC_LODS_TRY(search(lod, start, n_idx, d_ret, n_ret));
     if (n_ret > 0)

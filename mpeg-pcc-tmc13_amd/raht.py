@@ -166,7 +166,15 @@ class Context:
             C.c_void_p(d_qp_off or 0), C.c_void_p(d_attrs), C.c_void_p(d_coeffs), c))
 
     # ---- lifting transform (predictors given, host tier) -------------------
-    def _lift(self, forward, params, nc, ni, nw, indexes, attrs, coeffs, lcp, qp_off):
+    @staticmethod
+    def _partial(min_geom_node_size_log2, geom_num_points, n):
+        """the partial (spatially scalable) decode's two scalars, or None for a whole slice (the
+        existing entries)"""
+        if min_geom_node_size_log2 == 0 and geom_num_points is None:
+            return None
+        return int(min_geom_node_size_log2), int(n if geom_num_points is None else geom_num_points)
+
+    def _lift(self, forward, params, nc, ni, nw, indexes, attrs, coeffs, lcp, qp_off, partial=None):
         nc = np.ascontiguousarray(nc, dtype=np.int32)
         ni = np.ascontiguousarray(ni, dtype=np.int32)
         nw = np.ascontiguousarray(nw, dtype=np.int32)
@@ -184,6 +192,13 @@ class Context:
             c = co.shape[1]
             a = np.zeros((n, c), dtype=np.int32)
             fn = self._lib.gpcc_lift_inverse
+        if partial is not None:
+            assert not forward
+            _lib.check(self._lib.gpcc_lift_inverse_partial(
+                self._h, C.byref(params), n, c, partial[0], partial[1], nc.ctypes.data, ni.ctypes.data,
+                nw.ctypes.data, ix.ctypes.data, q.ctypes.data if q is not None else None, a.ctypes.data,
+                co.ctypes.data, l.ctypes.data))
+            return co, a, l
         _lib.check(fn(self._h, C.byref(params), n, c, nc.ctypes.data, ni.ctypes.data, nw.ctypes.data,
                       ix.ctypes.data, q.ctypes.data if q is not None else None, a.ctypes.data,
                       co.ctypes.data, l.ctypes.data))
@@ -194,9 +209,13 @@ class Context:
         (coeffs [n,c] coding order, recon [n,c] point order (clipped), lcp int8[32])"""
         return self._lift(True, params, nc, ni, nw, indexes, attrs, None, None, qp_off)
 
-    def lift_inverse(self, params, nc, ni, nw, indexes, coeffs, lcp=None, qp_off=None):
-        """decodeColorsLift / decodeReflectancesLift after the entropy decode -> recon [n,c]"""
-        return self._lift(False, params, nc, ni, nw, indexes, None, coeffs, lcp, qp_off)[1]
+    def lift_inverse(self, params, nc, ni, nw, indexes, coeffs, lcp=None, qp_off=None, min_geom_node_size_log2=0,
+                     geom_num_points=None):
+        """decodeColorsLift / decodeReflectancesLift after the entropy decode -> recon [n,c].
+        min_geom_node_size_log2 > 0 / geom_num_points: the predictors are those of a partially decoded
+        scalable-lifting slice of geom_num_points points (gpcc_lift_inverse_partial)"""
+        partial = self._partial(min_geom_node_size_log2, geom_num_points, len(nc))
+        return self._lift(False, params, nc, ni, nw, indexes, None, coeffs, lcp, qp_off, partial)[1]
 
     def lod_compute_weights(self, nc, dist2):
         """PCCPredictor::computeWeights -> (neighbour counts, 8-bit weights [n,3])"""
@@ -207,8 +226,10 @@ class Context:
                                                       w.ctypes.data))
         return nc, w
 
-    def lod_build(self, params, xyz):
-        """AttributeLods::generate -> dict(nc, ni, w, indexes, npl) in coding order"""
+    def lod_build(self, params, xyz, min_geom_node_size_log2=0, geom_num_points=None):
+        """AttributeLods::generate -> dict(nc, ni, w, indexes, npl) in coding order.
+        min_geom_node_size_log2 > 0 / geom_num_points: xyz is the cloud of a geometry decode that stopped
+        that many octree levels early, out of a slice of geom_num_points points (gpcc_lod_build_partial)"""
         xyz = np.ascontiguousarray(xyz, dtype=np.int32)
         n = xyz.shape[0]
         nc = np.zeros(n, np.int32)
@@ -217,6 +238,12 @@ class Context:
         idx = np.zeros(n, np.int32)
         npl = np.zeros(32, np.int32)
         nl = C.c_int32()
+        partial = self._partial(min_geom_node_size_log2, geom_num_points, n)
+        if partial is not None:
+            _lib.check(self._lib.gpcc_lod_build_partial(self._h, C.byref(params), xyz.ctypes.data, n, partial[0],
+                                                        partial[1], nc.ctypes.data, ni.ctypes.data, w.ctypes.data,
+                                                        idx.ctypes.data, npl.ctypes.data, C.byref(nl)))
+            return dict(nc=nc, ni=ni, w=w, indexes=idx, npl=npl[:nl.value].copy())
         _lib.check(self._lib.gpcc_lod_build(self._h, C.byref(params), xyz.ctypes.data, n, nc.ctypes.data,
                                             ni.ctypes.data, w.ctypes.data, idx.ctypes.data, npl.ctypes.data,
                                             C.byref(nl)))
@@ -336,13 +363,21 @@ class Context:
                                                    lcp.ctypes.data, idx.ctypes.data, n, c))
         return co, a, lcp, idx
 
-    def lift_decode_attr(self, lod_params, lift_params, xyz, coeffs, lcp=None):
-        """AttributeLods::generate + decode{Colors,Reflectances}Lift after the entropy decode -> recon [n,c]"""
+    def lift_decode_attr(self, lod_params, lift_params, xyz, coeffs, lcp=None, min_geom_node_size_log2=0,
+                         geom_num_points=None):
+        """AttributeLods::generate + decode{Colors,Reflectances}Lift after the entropy decode -> recon [n,c].
+        min_geom_node_size_log2 > 0 / geom_num_points: the partial decode (gpcc_lift_decode_attr_partial)"""
         xyz = np.ascontiguousarray(xyz, dtype=np.int32)
         co = np.ascontiguousarray(coeffs, dtype=np.int32)
         n, c = co.shape
         a = np.zeros((n, c), dtype=np.int32)
         l = np.zeros(32, dtype=np.int8) if lcp is None else np.ascontiguousarray(lcp, dtype=np.int8).copy()
+        partial = self._partial(min_geom_node_size_log2, geom_num_points, n)
+        if partial is not None:
+            _lib.check(self._lib.gpcc_lift_decode_attr_partial(self._h, C.byref(lod_params), C.byref(lift_params),
+                                                               xyz.ctypes.data, a.ctypes.data, co.ctypes.data,
+                                                               l.ctypes.data, None, n, c, partial[0], partial[1]))
+            return a
         _lib.check(self._lib.gpcc_lift_decode_attr(self._h, C.byref(lod_params), C.byref(lift_params),
                                                    xyz.ctypes.data, a.ctypes.data, co.ctypes.data,
                                                    l.ctypes.data, None, n, c))
@@ -419,17 +454,27 @@ class Context:
         return [list(npl[i, :nl[i]]) for i in range(s)]
 
     def dev_lift_attr(self, encode, lod_params, lift_params_list, offsets, d_xyz, d_attrs, d_coeffs, c, lcp=None,
-                      d_indexes=None):
+                      d_indexes=None, min_geom_node_size_log2=0, geom_num_points=None):
         """gpcc_dev_lift_encode_attr / _decode_attr on device buffers; lift_params_list: one
-        LiftParams per slice (filled with the LoD structure); -> lcp int8 [slices, 32]"""
+        LiftParams per slice (filled with the LoD structure); -> lcp int8 [slices, 32].
+        min_geom_node_size_log2 > 0 / geom_num_points (one full point count per slice): the partial
+        decode (gpcc_dev_lift_decode_attr_partial)"""
         from .params import LiftParams
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         s = len(offs) - 1
         arr = (LiftParams * s)(*lift_params_list)
         l = np.zeros((s, 32), dtype=np.int8) if lcp is None else np.ascontiguousarray(lcp, dtype=np.int8).copy()
         fn = self._lib.gpcc_dev_lift_encode_attr if encode else self._lib.gpcc_dev_lift_decode_attr
-        _lib.check(fn(self._h, C.byref(lod_params), arr, s, offs.ctypes.data_as(C.POINTER(C.c_int64)), d_xyz,
-                      d_attrs, d_coeffs, l.ctypes.data, d_indexes, c))
+        if min_geom_node_size_log2 != 0 or geom_num_points is not None:
+            assert not encode, "the encoder codes whole slices"
+            gnp = np.ascontiguousarray(np.diff(offs) if geom_num_points is None else geom_num_points, dtype=np.int32)
+            assert gnp.shape == (s,)
+            _lib.check(self._lib.gpcc_dev_lift_decode_attr_partial(
+                self._h, C.byref(lod_params), arr, s, offs.ctypes.data_as(C.POINTER(C.c_int64)), d_xyz, d_attrs,
+                d_coeffs, l.ctypes.data, d_indexes, c, int(min_geom_node_size_log2), gnp.ctypes.data))
+        else:
+            _lib.check(fn(self._h, C.byref(lod_params), arr, s, offs.ctypes.data_as(C.POINTER(C.c_int64)), d_xyz,
+                          d_attrs, d_coeffs, l.ctypes.data, d_indexes, c))
         for i in range(s):
             C.memmove(C.byref(lift_params_list[i]), C.byref(arr[i]), C.sizeof(LiftParams))
         return l

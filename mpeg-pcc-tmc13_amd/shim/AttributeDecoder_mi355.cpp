@@ -53,10 +53,14 @@ public:
     gpcc_clear_last_error();  // (what a decline of THIS slice reports is this slice's)
     _first.note(aps, abh, inter);  // (shim_common.hpp FirstLods: what the reference's object would cache)
     if (ours) {
-      // (scalable lifting: whole slices only -- no points skipped by a partial decode)
+      // (scalable lifting, points skipped by a partial decode: the lifting transform has an entry
+      // for it -- gpcc_lift_decode_attr_partial --, the predicting transform stays on the CPU)
       const bool whole =
         !aps.scalable_lifting_enabled_flag || geom_num_points_minus1 + 1 == int(cloud.getPointCount());
-      if (whole && on_device(sps, desc, aps, abh, minGeomNodeSizeLog2, payload, payloadLen, ctxtMem, cloud, inter)) {
+      const bool partialLift = !whole && aps.attr_encoding == AttributeEncoding::kLiftingTransform
+        && !inter.enableAttrInterPred && geom_num_points_minus1 + 1 > int(cloud.getPointCount());
+      if ((whole || partialLift)
+          && on_device(sps, desc, aps, abh, geom_num_points_minus1, minGeomNodeSizeLog2, payload, payloadLen, ctxtMem, cloud, inter)) {
         g_dec_device++;
         return;
       }
@@ -83,11 +87,14 @@ private:
   bool on_device(
     const SequenceParameterSet& sps, const AttributeDescription& desc,
     const AttributeParameterSet& aps, const AttributeBrickHeader& abh,
-    int minGeomNodeSizeLog2, const char* payload, size_t payloadLen,
+    int geom_num_points_minus1, int minGeomNodeSizeLog2, const char* payload, size_t payloadLen,
     AttributeContexts& ctxtMem, PCCPointSet3& cloud, AttributeInterPredParams& inter)
   {
     const int c = desc.attr_num_dimensions_minus1 + 1;
     const int n = int(cloud.getPointCount());
+    // a partially decoded scalable-lifting slice: fewer points than the slice header counts
+    const bool partial =
+      aps.scalable_lifting_enabled_flag && (minGeomNodeSizeLog2 > 0 || geom_num_points_minus1 + 1 != n);
     const bool interSlice = inter.enableAttrInterPred;   // (one component: the reflectance drivers)
     if ((c != 1 && c != 3) || n <= 0 || (interSlice && c != 1))
       return false;
@@ -158,7 +165,11 @@ private:
       if (lp.last_component_prediction_enabled_flag)
         for (size_t l = 0; l < abh.attrLcpCoeffs.size() && l < GPCC_MAX_LODS; l++)
           lcp[l] = abh.attrLcpCoeffs[l];
-      rc = gpcc_lift_decode_attr(ctx, &lod, &lp, xyz.data(), attrs.data(), values.data(), lcp, nullptr, n, c);
+      rc = partial
+        ? gpcc_lift_decode_attr_partial(
+            ctx, &lod, &lp, xyz.data(), attrs.data(), values.data(), lcp, nullptr, n, c,
+            minGeomNodeSizeLog2, geom_num_points_minus1 + 1)
+        : gpcc_lift_decode_attr(ctx, &lod, &lp, xyz.data(), attrs.data(), values.data(), lcp, nullptr, n, c);
     } else {
       pp.bitdepth = desc.bitdepth;
       pp.max_num_direct_predictors = aps.max_num_direct_predictors;

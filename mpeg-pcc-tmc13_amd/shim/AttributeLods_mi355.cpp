@@ -50,14 +50,17 @@ AttributeLods::generate(
   gpcc_lod_params lp;
   gpcc_ctx* ctx = gpcc_shim::process_context("the LoD build");
   const int n = int(cloud.getPointCount());
-  // (scalable lifting: whole slices only -- no points skipped by a partial decode)
-  const bool whole = !aps.scalable_lifting_enabled_flag || geom_num_points_minus1 + 1 == n;
+  // (scalable lifting: the points a partial decode skipped count in the structure -- the partial
+  // entry takes them; flatten_lod declines what it has no entry for)
+  const bool partial =
+    aps.scalable_lifting_enabled_flag && (minGeomNodeSizeLog2 > 0 || geom_num_points_minus1 + 1 != n);
+  const bool expressible = !partial || (geom_num_points_minus1 + 1 >= n && !attrInterPredParams.enableAttrInterPred);
   // attribute inter prediction: the search also looks into the reference frame
   // (gpcc_lod_build_inter); the transforms over the structure stay the reference's
   const bool inter = attrInterPredParams.enableAttrInterPred;
   const int nFrame = inter ? int(attrInterPredParams.referencePointCloud.getPointCount()) : 0;
   if (
-    ctx && n > 0 && whole && (!inter || nFrame > 0)
+    ctx && n > 0 && expressible && (!inter || nFrame > 0)
     && gpcc_shim::flatten_lod(aps, abh, minGeomNodeSizeLog2, attrInterPredParams, &lp, true)) {
     std::vector<int32_t> xyz;
     gpcc_shim::positions_of(cloud, &xyz);
@@ -72,7 +75,11 @@ AttributeLods::generate(
         ctx, &lp, xyz.data(), n, xyzFrame.data(), nFrame, abh.attrInterPredSearchRange,
         attrInterPredParams.frameDistance, nc.data(), ni.data(), nw.data(), idx.data(), npl, &nl,
         xr.data());
-    } else
+    } else if (partial)
+      rc = gpcc_lod_build_partial(
+        ctx, &lp, xyz.data(), n, minGeomNodeSizeLog2, geom_num_points_minus1 + 1, nc.data(),
+        ni.data(), nw.data(), idx.data(), npl, &nl);
+    else
       rc = gpcc_lod_build(
         ctx, &lp, xyz.data(), n, nc.data(), ni.data(), nw.data(), idx.data(), npl, &nl);
     if (rc == GPCC_OK) {

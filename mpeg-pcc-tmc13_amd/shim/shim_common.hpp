@@ -66,7 +66,9 @@ strict_check(const char* what)
 }
 
 // The LoD fields of the APS / ABH (buildPredictorsFast's inputs, hls.h:782-876).
-// false: the block cannot express these parameters -> CPU path
+// false: the block cannot express these parameters -> CPU path.  A partial decode
+// (minGeomNodeSizeLog2 > 0) has entries of its own for scalable lifting only (gpcc_lod_build_partial,
+// gpcc_lift_decode_attr_partial): the caller hands them the value and geom_num_points_minus1 + 1.
 inline bool
 flatten_lod(
   const pcc::AttributeParameterSet& aps, const pcc::AttributeBrickHeader& abh,
@@ -75,7 +77,11 @@ flatten_lod(
 {
   // (attribute inter prediction: only the caller that has an entry for it says so --
   // AttributeLods::generate -> gpcc_lod_build_inter)
-  if ((inter.enableAttrInterPred && !inter_allowed) || minGeomNodeSizeLog2 > 0)
+  if (inter.enableAttrInterPred && !inter_allowed)
+    return false;
+  if (minGeomNodeSizeLog2 > 0
+      && (!aps.scalable_lifting_enabled_flag || aps.attr_encoding != pcc::AttributeEncoding::kLiftingTransform
+          || inter.enableAttrInterPred || minGeomNodeSizeLog2 > 20))
     return false;
   if (aps.num_detail_levels_minus1 + 1 >= GPCC_MAX_LODS)
     return false;

@@ -642,6 +642,60 @@ int gpcc_pred_inverse_inter(
   int32_t* attrs, const int32_t* attrs_ref, int32_t n_ref,
   const int32_t* values);
 
+/* ------------------------------------------------------------------ */
+/* slice-level inter / intra decision (attrInterIntraSliceRDO)          */
+/* With the encoder option attrInterIntraSliceRDO (TMC3.cpp:1481) a reflectance slice coded with
+ * attribute inter prediction by the lifting or the predicting transform is coded TWICE and the
+ * cheaper result kept (AttributeEncoder::encode, AttributeEncoder.cpp:501-585;
+ * codeAttributeSecondPass(), PCCTMC3Common.h:293-296; only encodeReflectancesLift /
+ * encodeReflectancesPred have the second pass):
+ *   candidate 0, inter: over the coder object's cached structure, neighbours in the reference
+ *     frame allowed (as gpcc_lod_build_inter + gpcc_lift_forward_inter / gpcc_pred_forward_inter);
+ *   candidate 1, intra: enableAttrInterPred = false and the structure REGENERATED from this
+ *     slice's own aps / abh (:526-530, :558-562), whatever the cache was built with (as
+ *     gpcc_lift_encode_attr / gpcc_pred_encode_attr);
+ *   distEstimate = sum |reconstruction - source| over the points (:825-827, :1645-1646),
+ *   rateEstimate = the length of the arithmetic-coded stream (encoder.stop()),
+ *   cost = distEstimate + lambda * rateEstimate, intra wins iff costInter > costIntra.
+ *
+ * gpcc_lift_encode_attr_rdo / gpcc_pred_encode_attr_rdo run BOTH candidates in one call: positions,
+ * attributes and the reference frame are uploaded once, the two structures never leave the
+ * device, and one kernel sums both distortions (an int64 sum: exact, and equal to the reference's
+ * double, which only ever receives integers below 2^53).
+ *   lod_inter   the parameters the cached structure was built with; lod_intra this slice's own
+ *   lift / pred in: QP layers and tools (num_lods / num_points_in_lod are not read; not written)
+ *   xyz [n][3], attrs [n] the source, NOT written (a declined or failed call leaves the slice
+ *               to the CPU path untouched)
+ *   xyz_ref [n_ref][3], attrs_ref [n_ref], search_range, frame_distance as gpcc_lod_build_inter
+ *   values [2][n] out: each candidate's values in coding order (0 inter, 1 intra)
+ *   recon  [2][n] out: each candidate's clipped reconstruction, point order
+ *   dist   [2]    out: each candidate's distEstimate
+ * One component by signature.  GPCC_ERR_INVALID_ARG (checked ahead of the context): a null
+ * pointer, n <= 0, n_ref <= 0, search_range < 0.  GPCC_ERR_UNSUPPORTED as the single-candidate
+ * inter entries: scalable lifting, canonical_point_order_flag or a chunked sort in the inter
+ * build, QP regions; and a predicting candidate whose mode decisions do not settle
+ * (gpcc_pred_forward).  The candidates run one after the other on the context's stream. */
+int gpcc_lift_encode_attr_rdo(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra,
+  const gpcc_lift_params* lift, const int32_t* xyz, const int32_t* attrs, int32_t n,
+  const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref, int32_t search_range,
+  int32_t frame_distance, int32_t* values, int32_t* recon, int64_t* dist);
+int gpcc_pred_encode_attr_rdo(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra,
+  const gpcc_pred_params* pred, const int32_t* xyz, const int32_t* attrs, int32_t n,
+  const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref, int32_t search_range,
+  int32_t frame_distance, int32_t* values, int32_t* recon, int64_t* dist);
+
+/* The decision itself, plain host code (no context): AttributeInterPredParams::setLambda /
+ * getCost (PCCTMC3Common.h:287-291) verbatim --
+ *   lambda = std::pow(0.85 * std::pow(2., (qpMinus4 / 3)), 0.5)   with the INTEGER division,
+ *   cost   = distEstimate + lambda * rateEstimate                 in doubles, in this order,
+ * and *intra_wins = cost[0] > cost[1] (a tie keeps inter).  bytes_*: the arithmetic-coded length
+ * of each candidate (EntropyEncoder::stop()).  cost [2] out: inter, intra. */
+int gpcc_slice_rdo_choose(
+  int64_t dist_inter, int64_t bytes_inter, int64_t dist_intra, int64_t bytes_intra,
+  int32_t init_qp_minus4, int32_t* intra_wins, double* cost);
+
 
 /* Replaces the body of encodeColorsPred / encodeReflectancesPred minus the
  * entropy calls: attrs in source / out reconstruction, values [n][c] out (the

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "gpcc_dev_pred_encode_attr", "gpcc_dev_pred_decode_attr",
     "gpcc_lod_build_partial", "gpcc_lift_inverse_partial", "gpcc_lift_decode_attr_partial",
     "gpcc_dev_lift_decode_attr_partial",
+    "gpcc_lift_encode_attr_rdo", "gpcc_pred_encode_attr_rdo", "gpcc_slice_rdo_choose",
     "gpcc_ctx_reserve",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_guard_selftest",
@@ -139,6 +140,13 @@ def load():
                                                   i32, i32, i32, i32]
     lib.gpcc_dev_lift_decode_attr_partial.argtypes = [vp, C.POINTER(LodParams), vp, i32, i64p, vp, vp, vp, vp, vp, i32,
                                                       i32, vp]
+    # the slice-level inter / intra decision: both candidates in one call, and the decision (host code)
+    lib.gpcc_lift_encode_attr_rdo.argtypes = [vp, C.POINTER(LodParams), C.POINTER(LodParams), C.POINTER(LiftParams), vp, vp,
+                                              i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.gpcc_pred_encode_attr_rdo.argtypes = [vp, C.POINTER(LodParams), C.POINTER(LodParams), C.POINTER(PredParams), vp, vp,
+                                              i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.gpcc_slice_rdo_choose.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, C.POINTER(i32),
+                                          C.POINTER(C.c_double)]
     lib.gpcc_multi_create.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
     lib.gpcc_multi_destroy.argtypes = [vp]
     lib.gpcc_multi_destroy.restype = None

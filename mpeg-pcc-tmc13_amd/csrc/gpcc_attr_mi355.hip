@@ -50,6 +50,7 @@
 #include "morton_sort.hpp"
 #include "residual_bins.hpp"
 #include "recolour_kernels.hpp"
+#include "slice_rdo.hpp"
 
 using namespace gpcc;
 
@@ -3346,7 +3347,9 @@ int
 lod_build_core(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n,
   size_t extra_bytes, LodDeviceOut* out, bool xyz_on_device = false,
-  const LodInterFrame* frame = nullptr, const PartialDecode* partial = nullptr)
+  const LodInterFrame* frame = nullptr, const PartialDecode* partial = nullptr,
+  // the same positions, already on the device (a caller that builds twice over one upload); xyz stays the host copy
+  const int32_t* d_xyz_uploaded = nullptr)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
@@ -3434,7 +3437,7 @@ lod_build_core(
   if (!name)                                                    \
     return fail(GPCC_ERR_OUT_OF_MEMORY, "hipMalloc(" #name ")");
     DM(int32_t, d_xyz_own, 3 * N)
-    const int32_t* d_xyz = xyz_on_device ? xyz : d_xyz_own;
+    const int32_t* d_xyz = xyz_on_device ? xyz : d_xyz_uploaded ? d_xyz_uploaded : d_xyz_own;
     DM(int64_t, d_code, N)
     DM(int32_t, d_order, N)
     DM(int32_t, d_pos, 3 * N)
@@ -3476,7 +3479,7 @@ lod_build_core(
     int32_t* d_ticket = d_small;
     int32_t* d_error = d_small + 8;
     int32_t* d_counts = d_small + 16;
-    if (!xyz_on_device)
+    if (!xyz_on_device && !d_xyz_uploaded)
       HIP_TRY(h2d_user(ctx, d_xyz_own, xyz, sizeof(int32_t) * 3 * N, st));
     HIP_TRY(hipMemsetAsync(d_cell_state, 0, sizeof(uint32_t) * 4 * (N + 1), st));
     HIP_TRY(hipMemsetAsync(d_small, 0, sizeof(int32_t) * 64, st));
@@ -4081,6 +4084,185 @@ gpcc_lift_decode_attr_partial_impl(
   return lift_attr_driver(
     ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs),
     const_cast<int8_t*>(lcp_coeffs), indexes, n, c, &pd);
+}
+
+// ---- the slice-level inter / intra decision (attrInterIntraSliceRDO) -------------------------------
+// AttributeEncoder::encode codes a reflectance slice with attribute inter prediction twice when the
+// option is on (AttributeEncoder.cpp:501-585): over the cached structure with the reference frame, then
+// over a structure regenerated from the slice's own parameter sets without it, and keeps the cheaper.
+// Both candidates in one call: positions, attributes and the frame are uploaded once, the two
+// structures never leave the device, and slice_distortion_kernel (slice_rdo.hpp) sums both candidates'
+// |reconstruction - source|.
+
+// what can be refused without a context (so: on every machine)
+static int
+check_rdo_args(
+  const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra, const void* params, const int32_t* xyz,
+  const int32_t* attrs, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, const int32_t* values, const int32_t* recon, const int64_t* dist)
+{
+  if (!lod_inter || !lod_intra || !params || !xyz || !attrs || !xyz_ref || !attrs_ref || !values || !recon || !dist)
+    return fail(GPCC_ERR_INVALID_ARG, "null parameter block or buffer");
+  if (n <= 0 || n_ref <= 0 || search_range < 0)
+    return fail(GPCC_ERR_INVALID_ARG, "n <= 0, n_ref <= 0 or a negative search range");
+  if (lod_inter->scalable_lifting_enabled_flag || lod_intra->scalable_lifting_enabled_flag)
+    return fail(
+      GPCC_ERR_UNSUPPORTED, "inter prediction together with scalable lifting stays on the reference CPU path");
+  if (lod_inter->canonical_point_order_flag || lod_inter->max_points_per_sort_log2_plus1)
+    return fail(
+      GPCC_ERR_UNSUPPORTED,
+      "inter prediction together with canonical point order / a chunked sort stays on the reference CPU path");
+  return GPCC_OK;
+}
+
+// exactly one of lift / pred is given
+static int
+rdo_attr_driver(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra,
+  const gpcc_lift_params* lift, const gpcc_pred_params* pred, const int32_t* xyz, const int32_t* attrs,
+  int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref, int32_t search_range,
+  int32_t frame_distance, int32_t* values, int32_t* recon, int64_t* dist)
+{
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  if (n > (pred ? (1 << 27) : kMaxPoints) || n_ref > (pred ? (1 << 27) : kMaxPoints))
+    return fail(GPCC_ERR_INVALID_ARG, "too many points per call");
+  if ((lift ? lift->num_qp_regions : pred->num_qp_regions) != 0)
+    return fail(GPCC_ERR_UNSUPPORTED, "inter prediction together with QP regions stays on the reference CPU path");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t N = (size_t)n;
+  // what outlives a candidate's workspace (the arena is laid out again by the second build)
+  int32_t *d_xyz = nullptr, *d_orig = nullptr, *d_rec[2] = {nullptr, nullptr};
+  unsigned long long* d_dist = nullptr;
+  auto cleanup = [&]() {
+    pool_free(ctx, d_dist);
+    pool_free(ctx, d_rec[1]);
+    pool_free(ctx, d_rec[0]);
+    pool_free(ctx, d_orig);
+    pool_free(ctx, d_xyz);
+  };
+  // the lifting transform reads the frame's attributes in fixed point (launch_lift)
+  std::vector<int64_t> a_frame;
+  if (lift) {
+    a_frame.resize((size_t)n_ref);
+    for (size_t t = 0; t < a_frame.size(); t++)
+      a_frame[t] = (int64_t)attrs_ref[t] * 256;  // << kFixedPointAttributeShift
+  }
+  auto candidate = [&](int k) -> int {
+    const bool inter = k == 0;
+    const int nf = inter ? n_ref : 0;
+    const size_t scratch_bytes = lift ? lift_scratch_bytes(n + nf, 1) : pred_scratch_bytes(n, nf);
+    // neighbour indices behind the frame, values, lcp / icp block, scratch (+ a 256-byte round-up each)
+    const size_t extra = N * 12 + N * 4 + scratch_bytes + 8 * 1024;
+    LodInterFrame frame{xyz_ref, n_ref, search_range, frame_distance};
+    LodDeviceOut o;
+    int r = lod_build_core(ctx, inter ? lod_inter : lod_intra, xyz, n, extra, &o, false, inter ? &frame : nullptr, nullptr, d_xyz);
+    if (r)
+      return r;
+    Arena ar = ctx->arena;  // carve behind the LoD workspace
+    ar.used = o.arena_end;
+    int32_t* d_ni = inter ? ar.take<int32_t>(N * 3) : nullptr;
+    int32_t* d_values = ar.take<int32_t>(N);
+    int8_t* d_side = ar.take<int8_t>(GPCC_MAX_LODS * 3);  // (last-component / inter-component coefficients: none with one component)
+    char* scratch = ar.base + ar.used;
+    if (ar.used + scratch_bytes > ctx->arena.cap)
+      return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
+    const int32_t* ni = o.neigh_index;
+    if (inter) {
+      Timer tm(ctx, "rdo_frame_neighbours");
+      hipLaunchKernelGGL(
+        rdo_frame_neighbours_kernel, dim3(grid_for((int64_t)N * 3, 256)), dim3(256), 0, st, n, o.count, o.inter_ref,
+        o.neigh_index, d_ni);
+      ni = d_ni;
+    }
+    HIP_TRY(hipMemcpyAsync(d_rec[k], d_orig, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
+    if (lift) {
+      gpcc_lift_params lp = *lift;
+      lp.scalable_lifting_enabled_flag = 0;
+      lp.last_component_prediction_enabled_flag = 0;
+      lp.num_lods = (int)o.npl.size();
+      for (size_t i = 0; i < o.npl.size(); i++)
+        lp.num_points_in_lod[i] = o.npl[i];
+      r = check_lift_params(&lp, n, 1);
+      if (r)
+        return r;
+      LiftDev d{};
+      d.nc = o.count;
+      d.ni = ni;
+      d.nw = o.weight;
+      d.indexes = o.indexes;
+      d.attrs = d_rec[k];
+      d.coeffs = d_values;
+      r = launch_lift<1>(ctx, true, &lp, n, d, d_side, scratch, nf, inter ? a_frame.data() : nullptr);
+    } else {
+      gpcc_pred_params pp = *pred;
+      pp.scalable_lifting_enabled_flag = 0;
+      pp.inter_component_prediction_enabled_flag = 0;
+      pp.num_lods = (int)o.npl.size();
+      for (size_t i = 0; i < o.npl.size(); i++)
+        pp.num_points_in_lod[i] = o.npl[i];
+      r = check_pred_params(&pp, n, 1, true);
+      if (r)
+        return r;
+      PredDev d{};
+      d.nc = o.count;
+      d.ni = ni;
+      d.nw = o.weight;
+      d.indexes = o.indexes;
+      d.attrs = d_rec[k];
+      d.values = d_values;
+      r = launch_pred<1>(ctx, true, &pp, n, d, d_side, scratch, nf, inter ? attrs_ref : nullptr);
+    }
+    if (r)
+      return r;  // (a predicting candidate that did not settle: pred_encoder_unsettled)
+    int32_t h_err = 0;
+    HIP_TRY(d2h_user(ctx, values + (size_t)k * N, d_values, sizeof(int32_t) * N, st));
+    HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_err)
+      return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
+    return pred ? pred_check_error(ctx) : GPCC_OK;
+  };
+  auto run = [&]() -> int {
+    HIP_TRY(pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * N));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_orig, sizeof(int32_t) * N));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_rec[0], sizeof(int32_t) * N));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_rec[1], sizeof(int32_t) * N));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_dist, 2 * sizeof(unsigned long long)));
+    HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
+    HIP_TRY(h2d_user(ctx, d_orig, attrs, sizeof(int32_t) * N, st));
+    for (int k = 0; k < 2; k++) {
+      int r = candidate(k);
+      if (r)
+        return r;
+    }
+    HIP_TRY(hipMemsetAsync(d_dist, 0, 2 * sizeof(unsigned long long), st));
+    {
+      Timer tm(ctx, "slice_distortion");
+      SliceDistArgs a{};
+      a.rec[0] = d_rec[0];
+      a.rec[1] = d_rec[1];
+      a.orig = d_orig;
+      a.out = d_dist;
+      a.n = n;
+      a.num = 2;
+      hipLaunchKernelGGL(
+        slice_distortion_kernel, dim3(slice_distortion_grid(n)), dim3(kSliceDistBlock), 0, st, a);
+    }
+    HIP_TRY(hipGetLastError());
+    unsigned long long h_dist[2] = {0, 0};
+    HIP_TRY(d2h_user(ctx, recon, d_rec[0], sizeof(int32_t) * N, st));
+    HIP_TRY(d2h_user(ctx, recon + N, d_rec[1], sizeof(int32_t) * N, st));
+    HIP_TRY(hipMemcpyAsync(h_dist, d_dist, sizeof(h_dist), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    dist[0] = (int64_t)h_dist[0];
+    dist[1] = (int64_t)h_dist[1];
+    return GPCC_OK;
+  };
+  int r = run();
+  cleanup();
+  return r;
 }
 
 namespace {
@@ -4737,6 +4919,71 @@ gpcc_lift_decode_attr_partial(
       return counted(ctx, rc, n);
   }
   return counted(ctx, gpcc_lift_decode_attr_partial_impl(ctx, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c, min_geom_node_size_log2, geom_num_points), n);
+}
+
+int
+gpcc_lift_encode_attr_rdo(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra,
+  const gpcc_lift_params* lift, const int32_t* xyz, const int32_t* attrs, int32_t n, const int32_t* xyz_ref,
+  const int32_t* attrs_ref, int32_t n_ref, int32_t search_range, int32_t frame_distance, int32_t* values,
+  int32_t* recon, int64_t* dist)
+{
+  // (the arguments are checked first: the refusals need no context)
+  const int rc = check_rdo_args(
+    lod_inter, lod_intra, lift, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range, values, recon, dist);
+  if (rc)
+    return counted(ctx, rc, n);
+  return counted(
+    ctx,
+    rdo_attr_driver(
+      ctx, lod_inter, lod_intra, lift, nullptr, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range,
+      frame_distance, values, recon, dist),
+    n);
+}
+
+int
+gpcc_pred_encode_attr_rdo(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra,
+  const gpcc_pred_params* pred, const int32_t* xyz, const int32_t* attrs, int32_t n, const int32_t* xyz_ref,
+  const int32_t* attrs_ref, int32_t n_ref, int32_t search_range, int32_t frame_distance, int32_t* values,
+  int32_t* recon, int64_t* dist)
+{
+  const int rc = check_rdo_args(
+    lod_inter, lod_intra, pred, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range, values, recon, dist);
+  if (rc)
+    return counted(ctx, rc, n);
+  return counted(
+    ctx,
+    rdo_attr_driver(
+      ctx, lod_inter, lod_intra, nullptr, pred, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range,
+      frame_distance, values, recon, dist),
+    n);
+}
+
+// AttributeInterPredParams::setLambda / getCost (PCCTMC3Common.h:287-291) and the comparison of
+// AttributeEncoder.cpp:539, 571: the reference's expressions, the same double operations in the same order
+int
+gpcc_slice_rdo_choose(
+  int64_t dist_inter, int64_t bytes_inter, int64_t dist_intra, int64_t bytes_intra, int32_t init_qp_minus4,
+  int32_t* intra_wins, double* cost)
+{
+#pragma clang fp contract(off)  // (no fused multiply-add: the reference's build has none)
+  if (!intra_wins || !cost)
+    return fail(GPCC_ERR_INVALID_ARG, "null output");
+  if (dist_inter < 0 || dist_intra < 0 || bytes_inter < 0 || bytes_intra < 0 || bytes_inter > INT32_MAX
+      || bytes_intra > INT32_MAX)
+    return fail(GPCC_ERR_INVALID_ARG, "a negative estimate or a byte count beyond int");
+  const int qpMinus4 = init_qp_minus4;
+  const double lambda = std::pow(0.85 * std::pow(2., (qpMinus4 / 3)), 0.5);
+  // (distEstimate is a double that has summed integers, rateEstimate an int)
+  const double distInter = (double)dist_inter, distIntra = (double)dist_intra;
+  const int rateInter = (int)bytes_inter, rateIntra = (int)bytes_intra;
+  const double costInter = distInter + lambda * rateInter;
+  const double costIntra = distIntra + lambda * rateIntra;
+  cost[0] = costInter;
+  cost[1] = costIntra;
+  *intra_wins = costInter > costIntra ? 1 : 0;
+  return GPCC_OK;
 }
 
 int

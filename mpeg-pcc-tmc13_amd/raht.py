@@ -302,6 +302,36 @@ class Context:
                       ix.ctypes.data, a.ctypes.data, ar.ctypes.data, len(ar), v.ctypes.data))
         return v, a
 
+    def _encode_attr_rdo(self, fn, lod_inter, lod_intra, params, xyz, attrs, xyz_ref, attrs_ref, search_range,
+                         frame_distance):
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        xyz_ref = np.ascontiguousarray(xyz_ref, dtype=np.int32)
+        a = np.ascontiguousarray(attrs, dtype=np.int32).reshape(-1)
+        ar = np.ascontiguousarray(attrs_ref, dtype=np.int32).reshape(-1)
+        n = xyz.shape[0]
+        values = np.zeros((2, n), np.int32)
+        recon = np.zeros((2, n), np.int32)
+        dist = np.zeros(2, np.int64)
+        _lib.check(fn(self._h, C.byref(lod_inter), C.byref(lod_intra), C.byref(params), xyz.ctypes.data,
+                      a.ctypes.data, n, xyz_ref.ctypes.data, ar.ctypes.data, xyz_ref.shape[0], search_range,
+                      frame_distance, values.ctypes.data, recon.ctypes.data, dist.ctypes.data))
+        return values, recon, dist
+
+    def lift_encode_attr_rdo(self, lod_inter, lod_intra, lift_params, xyz, attrs, xyz_ref, attrs_ref, search_range,
+                             frame_distance=1):
+        """both candidates of the slice-level inter / intra decision of a reflectance lifting slice
+        (attrInterIntraSliceRDO) in one call -> (values [2,n] coding order, recon [2,n] point order,
+        dist int64 [2]); index 0 the inter candidate over lod_inter, 1 the intra candidate over
+        lod_intra.  attrs is not modified."""
+        return self._encode_attr_rdo(self._lib.gpcc_lift_encode_attr_rdo, lod_inter, lod_intra, lift_params, xyz,
+                                     attrs, xyz_ref, attrs_ref, search_range, frame_distance)
+
+    def pred_encode_attr_rdo(self, lod_inter, lod_intra, pred_params, xyz, attrs, xyz_ref, attrs_ref, search_range,
+                             frame_distance=1):
+        """lift_encode_attr_rdo for the predicting transform"""
+        return self._encode_attr_rdo(self._lib.gpcc_pred_encode_attr_rdo, lod_inter, lod_intra, pred_params, xyz,
+                                     attrs, xyz_ref, attrs_ref, search_range, frame_distance)
+
     def estimate_dist2(self, xyz, sampling_period=100, search_range=128, percentile=0.85):
         """pcc::estimateDist2 (encoder.cpp:1203 uses period 100, range 128) -> shift bits"""
         xyz = np.ascontiguousarray(xyz, dtype=np.int32)
@@ -638,3 +668,13 @@ class MultiContext:
         name = "gpcc_multi_pred_decode_attr" if predicting else "gpcc_multi_lift_decode_attr"
         self._lod_coder(name, lod_params, params_list, offsets, xyz, a, v, side, c)
         return a
+
+
+def slice_rdo_choose(dist_inter, bytes_inter, dist_intra, bytes_intra, init_qp_minus4):
+    """the slice-level inter / intra decision (gpcc_slice_rdo_choose: host code, no device)
+    -> (intra_wins bool, (cost_inter, cost_intra))"""
+    win = C.c_int32()
+    cost = (C.c_double * 2)()
+    _lib.check(_lib.load().gpcc_slice_rdo_choose(int(dist_inter), int(bytes_inter), int(dist_intra),
+                                                 int(bytes_intra), int(init_qp_minus4), C.byref(win), cost))
+    return bool(win.value), (cost[0], cost[1])

@@ -12,8 +12,9 @@
 // translation unit, which defines makeAttributeEncoder() with the original
 // signature and returns an AttributeEncoderIntf that
 //   * for a lifting / predicting slice without QP regions (with attribute inter prediction:
-//     one component, no slice-level inter / intra decision -- gpcc_lod_build_inter +
-//     gpcc_lift_forward_inter / gpcc_pred_forward_inter)
+//     one component -- gpcc_lod_build_inter + gpcc_lift_forward_inter / gpcc_pred_forward_inter;
+//     with the slice-level inter / intra decision, attrInterIntraSliceRDO, both candidates in one
+//     call -- gpcc_lift_encode_attr_rdo / gpcc_pred_encode_attr_rdo -- and gpcc_slice_rdo_choose)
 //     runs LoD build + transform (gpcc_lift_encode_attr / gpcc_pred_encode_attr),
 //     zero-run formation (gpcc_zero_run_pack) and binarisation
 //     (gpcc_binarise_symbols) on the MI355X, and then replays the binary
@@ -29,6 +30,7 @@
 //     reach the device's transform through seam 1 --, ...) to the reference's encoder unchanged.
 //
 // Built against the reference's headers; contains no reference code.
+#include <cstdlib>
 #include <memory>
 #include <vector>
 
@@ -99,10 +101,9 @@ private:
   {
     const int c = desc.attr_num_dimensions_minus1 + 1;
     const int n = int(cloud.getPointCount());
-    // attribute inter prediction: one component, and without the slice-level inter / intra
-    // decision (which codes the slice twice and compares, AttributeEncoder.cpp:520-585)
+    // attribute inter prediction: one component (the reference's reflectance drivers)
     const bool interSlice = inter.enableAttrInterPred;
-    if ((c != 1 && c != 3) || n <= 0 || inter.codeAttributeSecondPass() || (interSlice && c != 1))
+    if ((c != 1 && c != 3) || n <= 0 || (interSlice && c != 1))
       return false;
     gpcc_ctx* ctx = process_context("the attribute encoder");
     gpcc_lod_params lod;
@@ -115,10 +116,17 @@ private:
     if (interSlice && !qpSet.regions.empty())
       return false;  // (the entries with a reference frame take no QP regions)
     const bool lifting = aps.attr_encoding == AttributeEncoding::kLiftingTransform;
+    // the slice-level inter / intra decision codes the slice twice and compares (AttributeEncoder.cpp:501-585)
+    if (inter.codeAttributeSecondPass())
+      return rdo_on_device(sps, desc, aps, abh, ctxtMem, cloud, payload, inter, ctx, lod, qpSet, lifting);
 
     std::vector<int32_t> xyz, attrs, values(size_t(c) * n);
     positions_of(cloud, &xyz);
     attributes_of(cloud, c, &attrs);
+    // (the reflectance drivers sum the slice's distortion whenever the encoder option is on, :826, :1646)
+    std::vector<int32_t> source;
+    if (c == 1 && inter.attrInterIntraSliceRDO)
+      source = attrs;
 
     // ---- LoD build + transform: the values of every predictor in coding order ----
     int8_t lcp[GPCC_MAX_LODS] = {};
@@ -183,20 +191,9 @@ private:
     }
 
     // ---- zero runs and binary decisions, on the device where the values are ------
-    std::vector<int32_t> runs(n), syms(size_t(c) * n);
-    int32_t num_symbols = 0, trailing = 0;
-    if (gpcc_zero_run_pack(ctx, values.data(), n, c, 0, runs.data(), syms.data(), &num_symbols, &trailing))
-      return declined();
     int64_t num_bins = 0;
-    std::vector<uint8_t> bins(size_t(n) * (c == 3 ? 24 : 12) + 1024);
-    int rc = gpcc_binarise_symbols(
-      ctx, runs.data(), syms.data(), num_symbols, trailing, c, bins.data(), int64_t(bins.size()), &num_bins);
-    if (rc && num_bins > int64_t(bins.size())) {
-      bins.resize(size_t(num_bins));
-      rc = gpcc_binarise_symbols(
-        ctx, runs.data(), syms.data(), num_symbols, trailing, c, bins.data(), int64_t(bins.size()), &num_bins);
-    }
-    if (rc)
+    std::vector<uint8_t> bins;
+    if (!decisions_of(ctx, values.data(), n, c, &bins, &num_bins))
       return declined();
 
     // ---- from here on nothing can decline: the slice header may be written ---------
@@ -212,18 +209,7 @@ private:
     // (:113-121) does, driven by the decisions
     SliceContexts models(ctxtMem);
     EntropyEncoder ac;
-    ac.setBuffer(n * 3 * 2 + 1024, nullptr);
-    ac.enableBypassStream(sps.cabac_bypass_stream_enabled_flag);
-    ac.setBypassBinCodingWithoutProbUpdate(sps.bypass_bin_coding_without_prob_update);
-    ac.start();
-    for (int64_t i = 0; i < num_bins; i++) {
-      const int id = bins[i] >> 1, bin = bins[i] & 1;
-      if (id == 31)
-        ac.encode(bin);
-      else
-        ac.encode(bin, models.model(id));
-    }
-    const uint32_t len = ac.stop();
+    const uint32_t len = replay(sps, n, bins, num_bins, &models, &ac);
 
     abh.RAHTFilterTaps.assign(
       inter.paramsForInterRAHT.FilterTaps.begin(), inter.paramsForInterRAHT.FilterTaps.end());
@@ -231,12 +217,150 @@ private:
     payload->insert(payload->end(), ac.buffer(), ac.buffer() + len);
     ctxtMem = models.saved();
     store_attributes(attrs, c, &cloud);
-    // (the reference's reflectance drivers leave the slice's distortion estimate for the slice-level
-    // inter / intra decision here, AttributeEncoder.cpp:760, 826, 1554; such slices are declined above --
-    // codeAttributeSecondPass -- so nothing reads it: zero, not a value of an earlier slice)
-    if (c == 1)
-      inter.distEstimate = 0.;
+    if (c == 1) {
+      // what the reflectance drivers leave behind (AttributeEncoder.cpp:760, 826, 1554, 1646)
+      double d = 0.;
+      for (size_t i = 0; i < source.size(); i++)
+        d += std::abs(attrs[i] - source[i]);
+      inter.distEstimate = d;
+    }
     return true;
+  }
+
+  // ---- a reflectance slice with the slice-level inter / intra decision (attrInterIntraSliceRDO): what
+  //      AttributeEncoder::encode (:496-585, 613-634) does around its two runs of encodeReflectancesLift /
+  //      encodeReflectancesPred.  lod_inter: the structure the reference's cache holds (_first); the intra
+  //      candidate regenerates from THIS slice's parameter sets (:526-530, 558-562) ---------
+  bool rdo_on_device(
+    const SequenceParameterSet& sps, const AttributeDescription& desc,
+    const AttributeParameterSet& aps, AttributeBrickHeader& abh,
+    AttributeContexts& ctxtMem, PCCPointSet3& cloud, PayloadBuffer* payload,
+    AttributeInterPredParams& inter, gpcc_ctx* ctx, const gpcc_lod_params& lod_inter, const QpSet& qpSet,
+    bool lifting)
+  {
+    const int n = int(cloud.getPointCount());
+    gpcc_lod_params lod_intra;
+    if (!flatten_lod(aps, abh, 0, inter, &lod_intra, true))
+      return false;
+    const auto& frame = inter.referencePointCloud;
+    const int nFrame = int(frame.getPointCount());
+    if (nFrame <= 0 || !frame.hasReflectances()) {
+      std::fprintf(stderr, "gpcc: the reference frame of this slice has no reflectances; it stays on the CPU\n");
+      return false;
+    }
+    std::vector<int32_t> xyz, attrs, xyzFrame, attrsFrame(nFrame);
+    positions_of(cloud, &xyz);
+    attributes_of(cloud, 1, &attrs);
+    positions_of(frame, &xyzFrame);
+    for (int i = 0; i < nFrame; i++)
+      attrsFrame[i] = frame.getReflectance(i);
+
+    // ---- both candidates: structures, transforms, distortion sums ([0] inter, [1] intra) ----
+    std::vector<int32_t> values(size_t(2) * n), recon(size_t(2) * n);
+    int64_t dist[2] = {0, 0};
+    if (lifting) {
+      gpcc_lift_params lp{};
+      if (!flatten_qp(qpSet, &lp))
+        return false;
+      lp.bitdepth = desc.bitdepth;
+      lp.fixed_point_qp_offset = qpSet.fixedPointQpOffset;
+      if (gpcc_lift_encode_attr_rdo(
+            ctx, &lod_inter, &lod_intra, &lp, xyz.data(), attrs.data(), n, xyzFrame.data(), attrsFrame.data(), nFrame,
+            _first.abh.attrInterPredSearchRange, inter.frameDistance, values.data(), recon.data(), dist))
+        return declined();
+    } else {
+      gpcc_pred_params pp{};
+      if (!flatten_qp(qpSet, &pp))
+        return false;
+      pp.bitdepth = desc.bitdepth;
+      pp.max_num_direct_predictors = aps.max_num_direct_predictors;
+      pp.direct_avg_predictor_disabled_flag = aps.direct_avg_predictor_disabled_flag;
+      pp.adaptive_prediction_threshold = aps.adaptivePredictionThreshold(desc);
+      for (int k = 0; k < 3; k++)
+        pp.quant_neigh_weight[k] = aps.quant_neigh_weight[k];
+      pp.max_num_detail_levels = aps.maxNumDetailLevels();
+      if (gpcc_pred_encode_attr_rdo(
+            ctx, &lod_inter, &lod_intra, &pp, xyz.data(), attrs.data(), n, xyzFrame.data(), attrsFrame.data(), nFrame,
+            _first.abh.attrInterPredSearchRange, inter.frameDistance, values.data(), recon.data(), dist))
+        return declined();
+    }
+    int64_t num_bins[2] = {0, 0};
+    std::vector<uint8_t> bins[2];
+    for (int k = 0; k < 2; k++)
+      if (!decisions_of(ctx, values.data() + size_t(k) * n, n, 1, &bins[k], &num_bins[k]))
+        return declined();
+
+    // two coders, both from the incoming context state (PCCResidualsEncoder encoder / encoderOnlyIntra, :493, 499)
+    SliceContexts models[2] = {SliceContexts(ctxtMem), SliceContexts(ctxtMem)};
+    EntropyEncoder ac[2];
+    uint32_t len[2];
+    for (int k = 0; k < 2; k++)
+      len[k] = replay(sps, n, bins[k], num_bins[k], &models[k], &ac[k]);
+    int32_t intraWins = 0;
+    double cost[2];
+    if (gpcc_slice_rdo_choose(dist[0], len[0], dist[1], len[1], aps.init_qp_minus4, &intraWins, cost))
+      return declined();
+
+    // ---- from here on nothing can decline ---------
+    inter.setLambda(aps.init_qp_minus4);
+    const int w = intraWins ? 1 : 0;
+    if (intraWins) {
+      abh.enableAttrInterPred = false;
+      inter.enableAttrInterPred = false;
+      // the reference's cache now holds the structure of the intra run (_lods is not restored, :571-576)
+      _first.have = true;
+      _first.aps = aps;
+      _first.abh = abh;
+      _first.inter = false;
+    }
+    abh.RAHTFilterTaps.assign(
+      inter.paramsForInterRAHT.FilterTaps.begin(), inter.paramsForInterRAHT.FilterTaps.end());
+    write(sps, aps, abh, payload);
+    payload->insert(payload->end(), ac[w].buffer(), ac[w].buffer() + len[w]);
+    ctxtMem = models[w].saved();
+    store_attributes(std::vector<int32_t>(recon.begin() + size_t(w) * n, recon.begin() + size_t(w + 1) * n), 1, &cloud);
+    // (both estimates are left holding the intra run's values, :557, 566)
+    inter.distEstimate = double(dist[1]);
+    inter.rateEstimate = int(len[1]);
+    return true;
+  }
+
+  // zero runs and binary decisions of n values in coding order, on the device
+  static bool decisions_of(
+    gpcc_ctx* ctx, const int32_t* values, int n, int c, std::vector<uint8_t>* bins, int64_t* num_bins)
+  {
+    std::vector<int32_t> runs(n), syms(size_t(c) * n);
+    int32_t num_symbols = 0, trailing = 0;
+    if (gpcc_zero_run_pack(ctx, values, n, c, 0, runs.data(), syms.data(), &num_symbols, &trailing))
+      return false;
+    bins->resize(size_t(n) * (c == 3 ? 24 : 12) + 1024);
+    int rc = gpcc_binarise_symbols(
+      ctx, runs.data(), syms.data(), num_symbols, trailing, c, bins->data(), int64_t(bins->size()), num_bins);
+    if (rc && *num_bins > int64_t(bins->size())) {
+      bins->resize(size_t(*num_bins));
+      rc = gpcc_binarise_symbols(
+        ctx, runs.data(), syms.data(), num_symbols, trailing, c, bins->data(), int64_t(bins->size()), num_bins);
+    }
+    return rc == 0;
+  }
+
+  // the decisions on the reference's arithmetic coder and context models -> the coded length
+  static uint32_t replay(
+    const SequenceParameterSet& sps, int n, const std::vector<uint8_t>& bins, int64_t num_bins,
+    SliceContexts* models, EntropyEncoder* ac)
+  {
+    ac->setBuffer(n * 3 * 2 + 1024, nullptr);
+    ac->enableBypassStream(sps.cabac_bypass_stream_enabled_flag);
+    ac->setBypassBinCodingWithoutProbUpdate(sps.bypass_bin_coding_without_prob_update);
+    ac->start();
+    for (int64_t i = 0; i < num_bins; i++) {
+      const int id = bins[i] >> 1, bin = bins[i] & 1;
+      if (id == 31)
+        ac->encode(bin);
+      else
+        ac->encode(bin, models->model(id));
+    }
+    return uint32_t(ac->stop());
   }
 
   // ---- an intra RAHT slice: what AttributeEncoder::encode (:466-634) does around

@@ -1771,9 +1771,10 @@ host_transform_inter(
 
 // ---- lifting transform ---------------------------------------------------
 
-struct LiftDev {
+// what a launch sequence works on: the predictors of one slice on the device, its attributes and values
+struct LodCoderDev {
   const int32_t *nc, *ni, *nw, *indexes, *qp_off;
-  int32_t *attrs, *coeffs;
+  int32_t *attrs, *values;
 };
 
 int
@@ -1841,7 +1842,7 @@ template<int C>
 int
 launch_lift(
   gpcc_ctx* ctx, bool encoder, const gpcc_lift_params* p, int n,
-  const LiftDev& d, int8_t* d_lcp_io, char* scratch, int n_frame = 0,
+  const LodCoderDev& d, int8_t* d_lcp_io, char* scratch, int n_frame = 0,
   const int64_t* h_frame = nullptr, const PartialDecode* partial = nullptr)
 {
   hipStream_t st = ctx->stream;
@@ -1902,7 +1903,7 @@ launch_lift(
   cx.indexes = d.indexes;
   cx.qp_off = d.qp_off;
   cx.attrs = d.attrs;
-  cx.coeffs = d.coeffs;
+  cx.coeffs = d.values;
   cx.lcp = d_lcp_io;
   Arena ar;
   ar.base = scratch;
@@ -1989,142 +1990,14 @@ lift_scratch_bytes(int n, int c)
   return ar.used;
 }
 
+// ---- predicting transform ------------------------------------------------
+// inclusive scan of a[0 .. n) in place
 int
-host_lift(
-  gpcc_ctx* ctx, bool encoder, const gpcc_lift_params* p, int n, int c,
-  const int32_t* nc, const int32_t* ni, const int32_t* nw,
-  const int32_t* indexes, const int32_t* qp_off, int32_t* attrs,
-  int32_t* coeffs, int8_t* lcp,
-  // attribute inter prediction (null: none): inter_ref [n][3] marks the neighbours that live in
-  // the reference frame (ni is then a point index there), attrs_ref [n_frame][c] its attributes
-  const int32_t* inter_ref = nullptr, const int32_t* attrs_ref = nullptr, int n_frame = 0,
-  const PartialDecode* partial = nullptr)
+rc_scan(gpcc_ctx* ctx, int32_t* a, size_t n, long long* sums)
 {
-  if (!ctx)
-    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  int rcode = check_lift_params(p, n, c);
-  if (rcode)
-    return rcode;
-  if (partial) {
-    // (this entry IS the lifting transform: attr_encoding 2)
-    rcode = check_partial(*partial, n, p->scalable_lifting_enabled_flag != 0, 2, inter_ref != nullptr);
-    if (rcode)
-      return rcode;
-  }
-  if (!nc || !ni || !nw || !indexes || !attrs || !coeffs)
-    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
-  const bool lcp_on = c == 3 && p->last_component_prediction_enabled_flag;
-  if (lcp_on && !lcp)
-    return fail(GPCC_ERR_INVALID_ARG, "lcp_coeffs is null");
-  if (inter_ref) {
-    if (!attrs_ref || n_frame <= 0 || n_frame > kMaxPoints)
-      return fail(GPCC_ERR_INVALID_ARG, "reference frame: null, empty or too large");
-    if (c != 1 || p->scalable_lifting_enabled_flag)
-      return fail(
-        GPCC_ERR_UNSUPPORTED,
-        "inter prediction exists in the reference's reflectance lifting driver only, and not with scalable lifting");
-  } else
-    n_frame = 0;
-  for (int i = 0; i < n; i++) {
-    if (nc[i] < 0 || nc[i] > 3 || indexes[i] < 0 || indexes[i] >= n)
-      return fail(GPCC_ERR_INVALID_ARG, "bad neighbour count / index table");
-    for (int j = 0; j < nc[i]; j++) {
-      const int32_t v = ni[3 * (size_t)i + j];
-      if (inter_ref && inter_ref[3 * (size_t)i + j]) {
-        if (v < 0 || v >= n_frame)
-          return fail(GPCC_ERR_INVALID_ARG, "a neighbour outside the reference frame");
-      } else if (v < 0 || v >= i)
-        return fail(GPCC_ERR_INVALID_ARG, "a neighbour does not precede its predictor");
-    }
-  }
-  // neighbours in the reference frame are addressed behind the n predictors (launch_lift)
-  std::vector<int32_t> ni_frame;
-  std::vector<int64_t> a_frame;
-  if (inter_ref) {
-    ni_frame.assign(ni, ni + (size_t)n * 3);
-    for (int i = 0; i < n; i++)
-      for (int j = 0; j < nc[i]; j++)
-        if (inter_ref[3 * (size_t)i + j])
-          ni_frame[3 * (size_t)i + j] += n;
-    ni = ni_frame.data();
-    a_frame.resize((size_t)n_frame * c);
-    for (size_t t = 0; t < a_frame.size(); t++)
-      a_frame[t] = (int64_t)attrs_ref[t] * 256;  // << kFixedPointAttributeShift
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-
-  // one arena: inputs, outputs, scratch
-  Arena m;
-  auto carve = [&](Arena& ar, LiftDev& d, int32_t*& d_nc, int32_t*& d_ni,
-                   int32_t*& d_nw, int32_t*& d_ix, int32_t*& d_qp,
-                   int8_t*& d_lcp, char*& scratch) {
-    ar.reset();
-    d_nc = ar.take<int32_t>(n);
-    d_ni = ar.take<int32_t>((size_t)n * 3);
-    d_nw = ar.take<int32_t>((size_t)n * 3);
-    d_ix = ar.take<int32_t>(n);
-    d_qp = qp_off ? ar.take<int32_t>((size_t)n * 2) : nullptr;
-    d.attrs = ar.take<int32_t>((size_t)n * c);
-    d.coeffs = ar.take<int32_t>((size_t)n * c);
-    d_lcp = ar.take<int8_t>(GPCC_MAX_LODS);
-    scratch = ar.base ? ar.base + ar.used : nullptr;
-    ar.used += lift_scratch_bytes(n + n_frame, c);
-  };
-  LiftDev d{};
-  int32_t *d_nc, *d_ni, *d_nw, *d_ix, *d_qp;
-  int8_t* d_lcp;
-  char* scratch;
-  carve(m, d, d_nc, d_ni, d_nw, d_ix, d_qp, d_lcp, scratch);
-  rcode = ensure_arena(ctx, m.used);
-  if (rcode)
-    return rcode;
-  carve(ctx->arena, d, d_nc, d_ni, d_nw, d_ix, d_qp, d_lcp, scratch);
-  d.nc = d_nc;
-  d.ni = d_ni;
-  d.nw = d_nw;
-  d.indexes = d_ix;
-  d.qp_off = d_qp;
-  HIP_TRY(h2d_user(ctx, d_nc, nc, sizeof(int32_t) * n, st));
-  HIP_TRY(h2d_user(ctx, d_ni, ni, sizeof(int32_t) * n * 3, st));
-  HIP_TRY(h2d_user(ctx, d_nw, nw, sizeof(int32_t) * n * 3, st));
-  HIP_TRY(h2d_user(ctx, d_ix, indexes, sizeof(int32_t) * n, st));
-  if (qp_off)
-    HIP_TRY(h2d_user(ctx, d_qp, qp_off, sizeof(int32_t) * n * 2, st));
-  if (encoder) {
-    HIP_TRY(h2d_user(ctx, d.attrs, attrs, sizeof(int32_t) * n * c, st));
-  } else {
-    HIP_TRY(h2d_user(ctx, d.coeffs, coeffs, sizeof(int32_t) * n * c, st));
-    if (lcp_on)
-      HIP_TRY(hipMemcpyAsync(d_lcp, lcp, GPCC_MAX_LODS, hipMemcpyHostToDevice, st));
-  }
-  switch (c) {
-  case 1: rcode = launch_lift<1>(ctx, encoder, p, n, d, d_lcp, scratch, n_frame, a_frame.data(), partial); break;
-  case 2: rcode = launch_lift<2>(ctx, encoder, p, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-  default: rcode = launch_lift<3>(ctx, encoder, p, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-  }
-  if (rcode)
-    return rcode;
-  // (a_frame was staged by h2d_user: through the context's pinned buffer, or copied before the
-  // call returned -- the vector may go)
-  HIP_TRY(d2h_user(ctx, attrs, d.attrs, sizeof(int32_t) * n * c, st));
-  if (encoder) {
-    HIP_TRY(d2h_user(ctx, coeffs, d.coeffs, sizeof(int32_t) * n * c, st));
-    if (lcp_on)
-      HIP_TRY(hipMemcpyAsync(lcp, d_lcp, GPCC_MAX_LODS, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(kd_scan(ctx->stream, a, n, sums));
   return GPCC_OK;
 }
-
-
-// ---- predicting transform ------------------------------------------------
-struct PredDev {
-  const int32_t *nc, *ni, *nw, *indexes, *qp_off;
-  int32_t *attrs, *values;
-};
-
-int rc_scan(gpcc_ctx* ctx, int32_t* a, size_t n, long long* sums);  // (inclusive scan, defined with the recolour entry)
 
 // the predicting encoder's mode decisions did not settle (see pred_kernels.hpp)
 int
@@ -2199,7 +2072,7 @@ fill_u64_kernel(unsigned long long* p, unsigned long long v, int n)
 template<int C>
 int
 launch_pred(
-  gpcc_ctx* ctx, bool encoder, const gpcc_pred_params* p, int n, const PredDev& d,
+  gpcc_ctx* ctx, bool encoder, const gpcc_pred_params* p, int n, const LodCoderDev& d,
   int8_t* d_icp, char* scratch,
   // attribute inter prediction (n_frame > 0, one component): h_frame [n_frame] the reference
   // frame's reflectances (host memory); the caller has pointed the neighbours that live in
@@ -2422,33 +2295,75 @@ pred_check_error(gpcc_ctx* ctx)
   return GPCC_OK;
 }
 
+// ---- the two coders behind one description --------------------------------------------------
+// Everything the drivers below need to know about a coder: its parameter block, limits, the side block
+// (last-component / inter-component coefficients), scratch, launch sequence and closing error check.
+
+struct LiftCoder {
+  using Params = gpcc_lift_params;
+  using Frame = std::vector<int64_t>;  // the reference frame as the launcher takes it: fixed point
+  static constexpr int32_t kMaxN = kMaxPoints;
+  static constexpr size_t kSideBytes = GPCC_MAX_LODS;
+  static constexpr const char* kBadCount = "null buffer or attribute count not 1..3";
+  static constexpr const char* kSideNull = "lcp_coeffs is null";
+  static constexpr const char* kInterOnly =
+    "inter prediction exists in the reference's reflectance lifting driver only, and not with scalable lifting";
+  static bool count_ok(int c) { return c >= 1 && c <= 3; }
+  static bool side_on(const Params& p, int c) { return c == 3 && p.last_component_prediction_enabled_flag; }
+  static int check(const Params* p, int n, int c, bool) { return check_lift_params(p, n, c); }
+  static size_t scratch_bytes(int n, int c, int n_frame) { return lift_scratch_bytes(n + n_frame, c); }
+  static Frame stage_frame(const int32_t* attrs_ref, size_t count)
+  {
+    Frame f(count);
+    for (size_t t = 0; t < count; t++)
+      f[t] = (int64_t)attrs_ref[t] * 256;  // << kFixedPointAttributeShift
+    return f;
+  }
+  static int launch(
+    gpcc_ctx* ctx, bool encoder, const Params* p, int n, int c, const LodCoderDev& d, int8_t* d_side, char* scratch,
+    int n_frame, const Frame& frame, const PartialDecode* partial)
+  {
+    switch (c) {
+    case 1: return launch_lift<1>(ctx, encoder, p, n, d, d_side, scratch, n_frame, frame.data(), partial);
+    case 2: return launch_lift<2>(ctx, encoder, p, n, d, d_side, scratch, 0, nullptr, partial);
+    default: return launch_lift<3>(ctx, encoder, p, n, d, d_side, scratch, 0, nullptr, partial);
+    }
+  }
+  static int finish(gpcc_ctx*) { return GPCC_OK; }
+};
+
+struct PredCoder {
+  using Params = gpcc_pred_params;
+  using Frame = const int32_t*;  // the caller's reflectances as they are
+  static constexpr int32_t kMaxN = 1 << 27;
+  static constexpr size_t kSideBytes = GPCC_MAX_LODS * 3;
+  static constexpr const char* kBadCount = "null buffer or attribute count not 1 / 3";
+  static constexpr const char* kSideNull = "icp_coeffs is null";
+  static constexpr const char* kInterOnly =
+    "inter prediction exists in the reference's reflectance predicting driver only, and not over a scalable structure";
+  static bool count_ok(int c) { return c == 1 || c == 3; }
+  static bool side_on(const Params& p, int c) { return c == 3 && p.inter_component_prediction_enabled_flag; }
+  static int check(const Params* p, int n, int c, bool encoder) { return check_pred_params(p, n, c, encoder); }
+  static size_t scratch_bytes(int n, int, int n_frame) { return pred_scratch_bytes(n, n_frame); }
+  static Frame stage_frame(const int32_t* attrs_ref, size_t) { return attrs_ref; }
+  // (no partial decode of the predicting transform: check_partial refuses it)
+  static int launch(
+    gpcc_ctx* ctx, bool encoder, const Params* p, int n, int c, const LodCoderDev& d, int8_t* d_side, char* scratch,
+    int n_frame, const Frame& frame, const PartialDecode*)
+  {
+    return c == 1 ? launch_pred<1>(ctx, encoder, p, n, d, d_side, scratch, n_frame, frame)
+                  : launch_pred<3>(ctx, encoder, p, n, d, d_side, scratch);
+  }
+  static int finish(gpcc_ctx* ctx) { return pred_check_error(ctx); }
+};
+
+// ---- host tier: the caller brings the predictors ---------------------------------------------
+
+// inter_ref [n][3] (null: none) marks the neighbours that live in the reference frame: ni is then a point index there
 int
-host_pred(
-  gpcc_ctx* ctx, bool encoder, const gpcc_pred_params* p, int n, int c, const int32_t* nc,
-  const int32_t* ni, const int32_t* nw, const int32_t* indexes, const int32_t* qp_off,
-  int32_t* attrs, int32_t* values, int8_t* icp,
-  // attribute inter prediction (null: none), as host_lift
-  const int32_t* inter_ref = nullptr, const int32_t* attrs_ref = nullptr, int n_frame = 0)
+check_neighbour_tables(
+  int n, const int32_t* nc, const int32_t* ni, const int32_t* indexes, const int32_t* inter_ref, int n_frame)
 {
-  if (!ctx)
-    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  int rcode = check_pred_params(p, n, c, encoder);
-  if (rcode)
-    return rcode;
-  if (!nc || !ni || !nw || !indexes || !attrs || !values)
-    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
-  const bool icp_on = c == 3 && p->inter_component_prediction_enabled_flag;
-  if (icp_on && !icp)
-    return fail(GPCC_ERR_INVALID_ARG, "icp_coeffs is null");
-  if (inter_ref) {
-    if (!attrs_ref || n_frame <= 0 || n_frame > (1 << 27))
-      return fail(GPCC_ERR_INVALID_ARG, "reference frame: null, empty or too large");
-    if (c != 1 || p->scalable_lifting_enabled_flag)
-      return fail(
-        GPCC_ERR_UNSUPPORTED,
-        "inter prediction exists in the reference's reflectance predicting driver only, and not over a scalable structure");
-  } else
-    n_frame = 0;
   for (int i = 0; i < n; i++) {
     if (nc[i] < 0 || nc[i] > 3 || indexes[i] < 0 || indexes[i] >= n)
       return fail(GPCC_ERR_INVALID_ARG, "bad neighbour count / index table");
@@ -2461,22 +2376,73 @@ host_pred(
         return fail(GPCC_ERR_INVALID_ARG, "a neighbour does not precede its predictor");
     }
   }
-  // neighbours in the reference frame are addressed behind the n predictors (launch_pred)
-  std::vector<int32_t> ni_frame;
+  return GPCC_OK;
+}
+
+// neighbours in the reference frame are addressed behind the n predictors (launch_lift / launch_pred)
+std::vector<int32_t>
+frame_neighbours_behind(int n, const int32_t* nc, const int32_t* ni, const int32_t* inter_ref)
+{
+  std::vector<int32_t> out(ni, ni + (size_t)n * 3);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < nc[i]; j++)
+      if (inter_ref[3 * (size_t)i + j])
+        out[3 * (size_t)i + j] += n;
+  return out;
+}
+
+template<class Coder>
+int
+host_lod_coder(
+  gpcc_ctx* ctx, bool encoder, const typename Coder::Params* p, int n, int c, const int32_t* nc,
+  const int32_t* ni, const int32_t* nw, const int32_t* indexes, const int32_t* qp_off, int32_t* attrs,
+  int32_t* values, int8_t* side,
+  // attribute inter prediction (null: none): inter_ref as check_neighbour_tables, attrs_ref [n_frame][c] the
+  // frame's attributes
+  const int32_t* inter_ref = nullptr, const int32_t* attrs_ref = nullptr, int n_frame = 0,
+  const PartialDecode* partial = nullptr)
+{
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  int rcode = Coder::check(p, n, c, encoder);
+  if (rcode)
+    return rcode;
+  if (partial) {
+    // (only the lifting entries hand one over: attr_encoding 2)
+    rcode = check_partial(*partial, n, p->scalable_lifting_enabled_flag != 0, 2, inter_ref != nullptr);
+    if (rcode)
+      return rcode;
+  }
+  if (!nc || !ni || !nw || !indexes || !attrs || !values)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  const bool side_on = Coder::side_on(*p, c);
+  if (side_on && !side)
+    return fail(GPCC_ERR_INVALID_ARG, Coder::kSideNull);
   if (inter_ref) {
-    ni_frame.assign(ni, ni + (size_t)n * 3);
-    for (int i = 0; i < n; i++)
-      for (int j = 0; j < nc[i]; j++)
-        if (inter_ref[3 * (size_t)i + j])
-          ni_frame[3 * (size_t)i + j] += n;
+    if (!attrs_ref || n_frame <= 0 || n_frame > Coder::kMaxN)
+      return fail(GPCC_ERR_INVALID_ARG, "reference frame: null, empty or too large");
+    if (c != 1 || p->scalable_lifting_enabled_flag)
+      return fail(GPCC_ERR_UNSUPPORTED, Coder::kInterOnly);
+  } else
+    n_frame = 0;
+  rcode = check_neighbour_tables(n, nc, ni, indexes, inter_ref, n_frame);
+  if (rcode)
+    return rcode;
+  std::vector<int32_t> ni_frame;
+  typename Coder::Frame frame{};
+  if (inter_ref) {
+    ni_frame = frame_neighbours_behind(n, nc, ni, inter_ref);
     ni = ni_frame.data();
+    frame = Coder::stage_frame(attrs_ref, (size_t)n_frame * c);
   }
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t N = (size_t)n;
-  PredDev d{};
+
+  // one arena: inputs, outputs, scratch
+  LodCoderDev d{};
   int32_t *d_nc = nullptr, *d_ni = nullptr, *d_nw = nullptr, *d_ix = nullptr, *d_qp = nullptr;
-  int8_t* d_icp = nullptr;
+  int8_t* d_side = nullptr;
   char* scratch = nullptr;
   auto carve = [&](Arena& ar) {
     ar.reset();
@@ -2487,9 +2453,9 @@ host_pred(
     d_qp = qp_off ? ar.take<int32_t>(N * 2) : nullptr;
     d.attrs = ar.take<int32_t>(N * c);
     d.values = ar.take<int32_t>(N * c);
-    d_icp = ar.take<int8_t>(GPCC_MAX_LODS * 3);
+    d_side = ar.take<int8_t>(Coder::kSideBytes);
     scratch = ar.base ? ar.base + ar.used : nullptr;
-    ar.used += pred_scratch_bytes(n, n_frame);
+    ar.used += Coder::scratch_bytes(n, c, n_frame);
   };
   Arena m;
   carve(m);
@@ -2512,21 +2478,20 @@ host_pred(
     HIP_TRY(h2d_user(ctx, d.attrs, attrs, sizeof(int32_t) * N * c, st));
   } else {
     HIP_TRY(h2d_user(ctx, d.values, values, sizeof(int32_t) * N * c, st));
-    if (icp_on)
-      HIP_TRY(hipMemcpyAsync(d_icp, icp, GPCC_MAX_LODS * 3, hipMemcpyHostToDevice, st));
+    if (side_on)
+      HIP_TRY(hipMemcpyAsync(d_side, side, Coder::kSideBytes, hipMemcpyHostToDevice, st));
   }
-  rcode = c == 1 ? launch_pred<1>(ctx, encoder, p, n, d, d_icp, scratch, n_frame, attrs_ref)
-                 : launch_pred<3>(ctx, encoder, p, n, d, d_icp, scratch);
+  rcode = Coder::launch(ctx, encoder, p, n, c, d, d_side, scratch, n_frame, frame, partial);
   if (rcode)
     return rcode;
   HIP_TRY(d2h_user(ctx, attrs, d.attrs, sizeof(int32_t) * N * c, st));
   if (encoder) {
     HIP_TRY(d2h_user(ctx, values, d.values, sizeof(int32_t) * N * c, st));
-    if (icp_on)
-      HIP_TRY(hipMemcpyAsync(icp, d_icp, GPCC_MAX_LODS * 3, hipMemcpyDeviceToHost, st));
+    if (side_on)
+      HIP_TRY(hipMemcpyAsync(side, d_side, Coder::kSideBytes, hipMemcpyDeviceToHost, st));
   }
-  HIP_TRY(hipStreamSynchronize(st));
-  return pred_check_error(ctx);
+  HIP_TRY(hipStreamSynchronize(st));  // (ni_frame and frame were staged or copied by then)
+  return Coder::finish(ctx);
 }
 
 }  // namespace
@@ -3015,47 +2980,7 @@ gpcc_ctx_kernel_times(gpcc_ctx* ctx, gpcc_kernel_time* out, int32_t max_entries)
 }
 
 static int
-gpcc_raht_forward_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const int64_t* morton,
-  const int32_t* qp_off, int32_t* attrs, int32_t* coeffs, int32_t n, int32_t c)
-{
-  return host_transform(ctx, params, true, morton, qp_off, attrs, coeffs, n, c);
-}
-
-static int
-gpcc_raht_inverse_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const int64_t* morton,
-  const int32_t* qp_off, int32_t* attrs, const int32_t* coeffs, int32_t n,
-  int32_t c)
-{
-  return host_transform(
-    ctx, params, false, morton, qp_off, attrs, const_cast<int32_t*>(coeffs), n, c);
-}
-
-static int
-gpcc_dev_raht_forward_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, int32_t num_slices,
-  const int64_t* offsets, const void* d_morton, const void* d_qp_off,
-  void* d_attrs, void* d_coeffs, int32_t c)
-{
-  return dev_transform(
-    ctx, params, true, num_slices, offsets, d_morton, d_qp_off, d_attrs,
-    d_coeffs, c, ctx ? ctx->morton_bits : 0);
-}
-
-static int
-gpcc_dev_raht_inverse_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, int32_t num_slices,
-  const int64_t* offsets, const void* d_morton, const void* d_qp_off,
-  void* d_attrs, const void* d_coeffs, int32_t c)
-{
-  return dev_transform(
-    ctx, params, false, num_slices, offsets, d_morton, d_qp_off, d_attrs,
-    const_cast<void*>(d_coeffs), c, ctx ? ctx->morton_bits : 0);
-}
-
-static int
-gpcc_dev_attr_morton_sort_impl(
+dev_morton_sort(
   gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz,
   void* d_morton, void* d_order)
 {
@@ -3170,7 +3095,7 @@ gpcc_dev_attr_morton_sort_impl(
 }
 
 static int
-gpcc_attr_morton_sort_impl(
+host_morton_sort(
   gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int64_t* morton, int32_t* order)
 {
   if (!ctx)
@@ -3203,7 +3128,7 @@ gpcc_attr_morton_sort_impl(
     const int saved = ctx->morton_bits;
     ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)mx));
     const int64_t offs[2] = {0, n};
-    int r = gpcc_dev_attr_morton_sort_impl(ctx, 1, offs, d_x, d_m, d_o);
+    int r = dev_morton_sort(ctx, 1, offs, d_x, d_m, d_o);
     ctx->morton_bits = saved;
     if (r)
       return r;
@@ -3218,44 +3143,7 @@ gpcc_attr_morton_sort_impl(
 }
 
 static int
-gpcc_lift_forward_impl(
-  gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n, int32_t c,
-  const int32_t* neigh_count, const int32_t* neigh_index,
-  const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off,
-  int32_t* attrs, int32_t* coeffs, int8_t* lcp_coeffs)
-{
-  return host_lift(
-    ctx, true, params, n, c, neigh_count, neigh_index, neigh_weight, indexes,
-    qp_off, attrs, coeffs, lcp_coeffs);
-}
-
-static int
-gpcc_lift_inverse_impl(
-  gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n, int32_t c,
-  const int32_t* neigh_count, const int32_t* neigh_index,
-  const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off,
-  int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs)
-{
-  return host_lift(
-    ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes,
-    qp_off, attrs, const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs));
-}
-
-static int
-gpcc_lift_inverse_partial_impl(
-  gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n, int32_t c, int32_t min_geom_node_size_log2,
-  int32_t geom_num_points, const int32_t* neigh_count, const int32_t* neigh_index,
-  const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off, int32_t* attrs,
-  const int32_t* coeffs, const int8_t* lcp_coeffs)
-{
-  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
-  return host_lift(
-    ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs,
-    const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs), nullptr, nullptr, 0, &pd);
-}
-
-static int
-gpcc_lod_compute_weights_impl(
+lod_compute_weights(
   gpcc_ctx* ctx, int32_t n, int32_t* neigh_count, const uint64_t* dist2,
   int32_t* neigh_weight)
 {
@@ -3489,7 +3377,7 @@ lod_build_core(
       const int saved = ctx->morton_bits;
       ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)mx));
       const int64_t offs[2] = {0, n};
-      int r = gpcc_dev_attr_morton_sort_impl(ctx, 1, offs, d_xyz, d_code, d_order);
+      int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_code, d_order);
       ctx->morton_bits = saved;
       if (r)
         return r;
@@ -3526,7 +3414,7 @@ lod_build_core(
       const int saved = ctx->morton_bits;
       ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)fmx));
       const int64_t offs[2] = {0, (int64_t)NF};
-      int r = gpcc_dev_attr_morton_sort_impl(ctx, 1, offs, d_fxyz, d_fcode, d_forder);
+      int r = dev_morton_sort(ctx, 1, offs, d_fxyz, d_fcode, d_forder);
       ctx->morton_bits = saved;
       if (r)
         return r;
@@ -3834,12 +3722,19 @@ lod_build_core(
   return run();
 }
 
-}  // namespace
+int
+lod_error_word(gpcc_ctx* ctx, const LodDeviceOut& o)
+{
+  int32_t h_err = 0;
+  HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (h_err)
+    return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
+  return GPCC_OK;
+}
 
-extern "C" {
-
-static int
-gpcc_lod_build_impl(
+int
+lod_build(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n,
   int32_t* neigh_count, int32_t* neigh_index, int32_t* neigh_weight,
   int32_t* indexes, int32_t* num_points_in_lod, int32_t* num_lods,
@@ -3868,8 +3763,8 @@ gpcc_lod_build_impl(
   return GPCC_OK;
 }
 
-static int
-gpcc_lod_build_inter_impl(
+int
+lod_build_inter(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n, const int32_t* xyz_ref,
   int32_t n_ref, int32_t search_range, int32_t frame_distance, int32_t* neigh_count,
   int32_t* neigh_index, int32_t* neigh_weight, int32_t* indexes, int32_t* num_points_in_lod,
@@ -3900,190 +3795,147 @@ gpcc_lod_build_inter_impl(
   return GPCC_OK;
 }
 
-// The predicting attribute coder of one slice minus the entropy loop --
-// AttributeLods::generate + encodeColorsPred / encodeReflectancesPred
-// (AttributeEncoder.cpp:575-579, 749-853, 1075-1210) resp. decode...Pred
-// (AttributeDecoder.cpp:292-296, 328-523): the predictors never leave the
-// device.
-static int
-pred_attr_driver(
-  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, gpcc_pred_params* pred,
-  const int32_t* xyz, int32_t* attrs, int32_t* values, int8_t* icp, int32_t* indexes,
-  int32_t n, int32_t c)
+// ---- one slice over a structure that lod_build_core left on the device -----------------------
+
+// the blocks of one slice behind the LoD workspace; a caller names those it needs beside side block and scratch
+struct SliceBlocks {
+  int32_t *ni = nullptr, *qp = nullptr, *attrs = nullptr, *values = nullptr;
+  int8_t* side = nullptr;
+  char* scratch = nullptr;
+};
+enum : unsigned {
+  kBlkFrameNi = 1,  // [n][3] neighbour indices with the frame's behind the n predictors
+  kBlkQp = 2,       // [n][2] region QP offsets per point
+  kBlkAttrs = 4,    // [n][c]; without it the caller points the coder at a buffer of its own
+  kBlkValues = 8,
+};
+
+template<class Coder>
+SliceBlocks
+carve_slice(Arena& ar, size_t N, int c, int n_frame, unsigned what)
 {
-  if (!ctx)
-    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  if (!pred || !attrs || !values || (c != 1 && c != 3))
-    return fail(GPCC_ERR_INVALID_ARG, "null buffer or attribute count not 1 / 3");
-  const bool icp_on = c == 3 && pred->inter_component_prediction_enabled_flag;
-  if (icp_on && !icp)
-    return fail(GPCC_ERR_INVALID_ARG, "icp_coeffs is null");
-  const size_t N = (size_t)(n > 0 ? n : 0);
-  const size_t extra = ((N * c * sizeof(int32_t) + 255) & ~size_t(255)) * 2 + 512
-    + pred_scratch_bytes(n > 0 ? n : 1) + 1024 + N * 8 + 256;
-  LodDeviceOut o;
-  int r = lod_build_core(ctx, lod, xyz, n, extra, &o);
-  if (r)
-    return r;
-  pred->scalable_lifting_enabled_flag = lod->scalable_lifting_enabled_flag != 0;
-  pred->num_lods = (int)o.npl.size();
+  SliceBlocks b;
+  if (what & kBlkFrameNi)
+    b.ni = ar.take<int32_t>(N * 3);
+  if (what & kBlkQp)
+    b.qp = ar.take<int32_t>(N * 2);
+  if (what & kBlkAttrs)
+    b.attrs = ar.take<int32_t>(N * c);
+  if (what & kBlkValues)
+    b.values = ar.take<int32_t>(N * c);
+  b.side = ar.take<int8_t>(Coder::kSideBytes);
+  b.scratch = ar.base ? ar.base + ar.used : nullptr;
+  ar.used += Coder::scratch_bytes((int)N, c, n_frame);
+  return b;
+}
+
+// what lod_build_core has to reserve behind its workspace: the same carve, measured
+template<class Coder>
+size_t
+slice_reserve(int n, int c, int n_frame, unsigned what)
+{
+  Arena measure;
+  carve_slice<Coder>(measure, (size_t)std::max(n, 0), c, n_frame, what);
+  return measure.used;
+}
+
+// The structure's level sizes go into the parameter block, the blocks are placed, the coder runs, both error
+// words are read.  stage(blocks, dev) is the caller's part between placing and launching (uploads; it may
+// point dev at buffers of its own), collect(blocks) what it copies back ahead of the synchronisation.
+template<class Coder, class Stage, class Collect>
+int
+code_slice(
+  gpcc_ctx* ctx, bool encoder, bool scalable, typename Coder::Params* p, int n, int c, const LodDeviceOut& o,
+  unsigned what, int n_frame, const typename Coder::Frame& frame, const PartialDecode* partial, Stage&& stage,
+  Collect&& collect)
+{
+  p->scalable_lifting_enabled_flag = scalable;
+  p->num_lods = (int)o.npl.size();
   for (size_t i = 0; i < o.npl.size(); i++)
-    pred->num_points_in_lod[i] = o.npl[i];
-  r = check_pred_params(pred, n, c, encoder);
+    p->num_points_in_lod[i] = o.npl[i];
+  int r = Coder::check(p, n, c, encoder);
   if (r)
     return r;
-  hipStream_t st = ctx->stream;
   Arena ar = ctx->arena;  // carve behind the LoD workspace
   ar.used = o.arena_end;
-  PredDev d{};
+  const SliceBlocks b = carve_slice<Coder>(ar, (size_t)n, c, n_frame, what);
+  if (ar.used > ctx->arena.cap)
+    return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
+  LodCoderDev d{};
   d.nc = o.count;
   d.ni = o.neigh_index;
   d.nw = o.weight;
   d.indexes = o.indexes;
-  r = qp_regions_to_points(pred, o.xyz, n, ar.take<int32_t>(N * 2), st, &d.qp_off);
+  d.attrs = b.attrs;
+  d.values = b.values;
+  if (what & kBlkQp) {
+    r = qp_regions_to_points(p, o.xyz, n, b.qp, ctx->stream, &d.qp_off);
+    if (r)
+      return r;
+  }
+  r = stage(b, d);
   if (r)
     return r;
-  d.attrs = ar.take<int32_t>(N * c);
-  d.values = ar.take<int32_t>(N * c);
-  int8_t* d_icp = ar.take<int8_t>(GPCC_MAX_LODS * 3);
-  char* scratch = ar.base + ar.used;
-  if (ar.used + pred_scratch_bytes(n) > ctx->arena.cap)
-    return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
-  if (encoder) {
-    HIP_TRY(h2d_user(ctx, d.attrs, attrs, sizeof(int32_t) * N * c, st));
-  } else {
-    HIP_TRY(h2d_user(ctx, d.values, values, sizeof(int32_t) * N * c, st));
-    if (icp_on)
-      HIP_TRY(hipMemcpyAsync(d_icp, icp, GPCC_MAX_LODS * 3, hipMemcpyHostToDevice, st));
-  }
-  r = c == 1 ? launch_pred<1>(ctx, encoder, pred, n, d, d_icp, scratch)
-             : launch_pred<3>(ctx, encoder, pred, n, d, d_icp, scratch);
+  r = Coder::launch(ctx, encoder, p, n, c, d, b.side, b.scratch, n_frame, frame, partial);
+  if (r)
+    return r;  // (a predicting encoder that did not settle: pred_encoder_unsettled)
+  r = collect(b);
   if (r)
     return r;
-  int32_t h_err = 0;
-  HIP_TRY(d2h_user(ctx, attrs, d.attrs, sizeof(int32_t) * N * c, st));
-  if (encoder) {
-    HIP_TRY(d2h_user(ctx, values, d.values, sizeof(int32_t) * N * c, st));
-    if (icp_on)
-      HIP_TRY(hipMemcpyAsync(icp, d_icp, GPCC_MAX_LODS * 3, hipMemcpyDeviceToHost, st));
-  }
-  if (indexes)
-    HIP_TRY(d2h_user(ctx, indexes, o.indexes, sizeof(int32_t) * N, st));
-  HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h_err)
-    return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
-  return pred_check_error(ctx);
+  r = lod_error_word(ctx, o);
+  if (r)
+    return r;
+  return Coder::finish(ctx);
 }
 
-// The lifting attribute coder of one slice minus the entropy loop --
-// AttributeLods::generate + encodeColorsLift / encodeReflectancesLift
-// (AttributeEncoder.cpp:575-579, 1379-1648) resp. decode...Lift
-// (AttributeDecoder.cpp:292-296, 678-857): the predictors never leave the
-// device.
-static int
-lift_attr_driver(
-  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, gpcc_lift_params* lift,
-  const int32_t* xyz, int32_t* attrs, int32_t* coeffs, int8_t* lcp, int32_t* indexes,
-  int32_t n, int32_t c, const PartialDecode* partial = nullptr)
+// The attribute coder of one slice minus the entropy loop -- AttributeLods::generate + encodeColorsLift /
+// encodeReflectancesLift (AttributeEncoder.cpp:575-579, 1379-1648) resp. ...Pred (:749-853, 1075-1210), or
+// decode...Lift (AttributeDecoder.cpp:292-296, 678-857) resp. ...Pred (:328-523): the predictors never leave
+// the device.
+template<class Coder>
+int
+slice_attr_driver(
+  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, typename Coder::Params* p, const int32_t* xyz,
+  int32_t* attrs, int32_t* values, int8_t* side, int32_t* indexes, int32_t n, int32_t c,
+  const PartialDecode* partial = nullptr)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  if (!lift || !attrs || !coeffs || c < 1 || c > 3)
-    return fail(GPCC_ERR_INVALID_ARG, "null buffer or attribute count not 1..3");
-  const bool lcp_on = c == 3 && lift->last_component_prediction_enabled_flag;
-  if (lcp_on && !lcp)
-    return fail(GPCC_ERR_INVALID_ARG, "lcp_coeffs is null");
-  const size_t N = (size_t)(n > 0 ? n : 0);
-  const size_t extra = ((N * c * sizeof(int32_t) + 255) & ~size_t(255)) * 2 + 256
-    + lift_scratch_bytes(n > 0 ? n : 1, c) + 1024 + N * 8 + 256;
+  if (!p || !attrs || !values || !Coder::count_ok(c))
+    return fail(GPCC_ERR_INVALID_ARG, Coder::kBadCount);
+  const bool side_on = Coder::side_on(*p, c);
+  if (side_on && !side)
+    return fail(GPCC_ERR_INVALID_ARG, Coder::kSideNull);
+  const unsigned what = kBlkQp | kBlkAttrs | kBlkValues;
   LodDeviceOut o;
-  int r = lod_build_core(ctx, lod, xyz, n, extra, &o, false, nullptr, partial);
-  if (r)
-    return r;
-  lift->scalable_lifting_enabled_flag = lod->scalable_lifting_enabled_flag != 0;
-  lift->num_lods = (int)o.npl.size();
-  for (size_t i = 0; i < o.npl.size(); i++)
-    lift->num_points_in_lod[i] = o.npl[i];
-  r = check_lift_params(lift, n, c);
+  int r = lod_build_core(ctx, lod, xyz, n, slice_reserve<Coder>(n, c, 0, what), &o, false, nullptr, partial);
   if (r)
     return r;
   hipStream_t st = ctx->stream;
-  Arena ar = ctx->arena;  // carve behind the LoD workspace
-  ar.used = o.arena_end;
-  LiftDev d{};
-  d.nc = o.count;
-  d.ni = o.neigh_index;
-  d.nw = o.weight;
-  d.indexes = o.indexes;
-  r = qp_regions_to_points(lift, o.xyz, n, ar.take<int32_t>(N * 2), st, &d.qp_off);
-  if (r)
-    return r;
-  d.attrs = ar.take<int32_t>(N * c);
-  d.coeffs = ar.take<int32_t>(N * c);
-  int8_t* d_lcp = ar.take<int8_t>(GPCC_MAX_LODS);
-  char* scratch = ar.base + ar.used;
-  if (ar.used + lift_scratch_bytes(n, c) > ctx->arena.cap)
-    return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
-  if (encoder) {
-    HIP_TRY(h2d_user(ctx, d.attrs, attrs, sizeof(int32_t) * N * c, st));
-  } else {
-    HIP_TRY(h2d_user(ctx, d.coeffs, coeffs, sizeof(int32_t) * N * c, st));
-    if (lcp_on)
-      HIP_TRY(hipMemcpyAsync(d_lcp, lcp, GPCC_MAX_LODS, hipMemcpyHostToDevice, st));
-  }
-  switch (c) {
-  case 1: r = launch_lift<1>(ctx, encoder, lift, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-  case 2: r = launch_lift<2>(ctx, encoder, lift, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-  default: r = launch_lift<3>(ctx, encoder, lift, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-  }
-  if (r)
-    return r;
-  int32_t h_err = 0;
-  HIP_TRY(d2h_user(ctx, attrs, d.attrs, sizeof(int32_t) * N * c, st));
-  if (encoder) {
-    HIP_TRY(d2h_user(ctx, coeffs, d.coeffs, sizeof(int32_t) * N * c, st));
-    if (lcp_on)
-      HIP_TRY(hipMemcpyAsync(lcp, d_lcp, GPCC_MAX_LODS, hipMemcpyDeviceToHost, st));
-  }
-  if (indexes)
-    HIP_TRY(d2h_user(ctx, indexes, o.indexes, sizeof(int32_t) * N, st));
-  HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h_err)
-    return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
-  return GPCC_OK;
-}
-
-static int
-gpcc_lift_encode_attr_impl(
-  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
-  int32_t* attrs, int32_t* coeffs, int8_t* lcp_coeffs, int32_t* indexes, int32_t n, int32_t c)
-{
-  return lift_attr_driver(ctx, true, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c);
-}
-
-static int
-gpcc_lift_decode_attr_impl(
-  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
-  int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs, int32_t* indexes, int32_t n,
-  int32_t c)
-{
-  return lift_attr_driver(
-    ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs),
-    const_cast<int8_t*>(lcp_coeffs), indexes, n, c);
-}
-
-static int
-gpcc_lift_decode_attr_partial_impl(
-  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
-  int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs, int32_t* indexes, int32_t n,
-  int32_t c, int32_t min_geom_node_size_log2, int32_t geom_num_points)
-{
-  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
-  return lift_attr_driver(
-    ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs),
-    const_cast<int8_t*>(lcp_coeffs), indexes, n, c, &pd);
+  const size_t bytes = sizeof(int32_t) * (size_t)n * c;
+  return code_slice<Coder>(
+    ctx, encoder, lod->scalable_lifting_enabled_flag != 0, p, n, c, o, what, 0, {}, partial,
+    [&](const SliceBlocks& b, LodCoderDev&) -> int {
+      if (encoder) {
+        HIP_TRY(h2d_user(ctx, b.attrs, attrs, bytes, st));
+      } else {
+        HIP_TRY(h2d_user(ctx, b.values, values, bytes, st));
+        if (side_on)
+          HIP_TRY(hipMemcpyAsync(b.side, side, Coder::kSideBytes, hipMemcpyHostToDevice, st));
+      }
+      return GPCC_OK;
+    },
+    [&](const SliceBlocks& b) -> int {
+      HIP_TRY(d2h_user(ctx, attrs, b.attrs, bytes, st));
+      if (encoder) {
+        HIP_TRY(d2h_user(ctx, values, b.values, bytes, st));
+        if (side_on)
+          HIP_TRY(hipMemcpyAsync(side, b.side, Coder::kSideBytes, hipMemcpyDeviceToHost, st));
+      }
+      if (indexes)
+        HIP_TRY(d2h_user(ctx, indexes, o.indexes, sizeof(int32_t) * (size_t)n, st));
+      return GPCC_OK;
+    });
 }
 
 // ---- the slice-level inter / intra decision (attrInterIntraSliceRDO) -------------------------------
@@ -4095,7 +3947,7 @@ gpcc_lift_decode_attr_partial_impl(
 // |reconstruction - source|.
 
 // what can be refused without a context (so: on every machine)
-static int
+int
 check_rdo_args(
   const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra, const void* params, const int32_t* xyz,
   const int32_t* attrs, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
@@ -4115,19 +3967,19 @@ check_rdo_args(
   return GPCC_OK;
 }
 
-// exactly one of lift / pred is given
-static int
+template<class Coder>
+int
 rdo_attr_driver(
   gpcc_ctx* ctx, const gpcc_lod_params* lod_inter, const gpcc_lod_params* lod_intra,
-  const gpcc_lift_params* lift, const gpcc_pred_params* pred, const int32_t* xyz, const int32_t* attrs,
-  int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref, int32_t search_range,
-  int32_t frame_distance, int32_t* values, int32_t* recon, int64_t* dist)
+  const typename Coder::Params* params, const int32_t* xyz, const int32_t* attrs, int32_t n, const int32_t* xyz_ref,
+  const int32_t* attrs_ref, int32_t n_ref, int32_t search_range, int32_t frame_distance, int32_t* values,
+  int32_t* recon, int64_t* dist)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  if (n > (pred ? (1 << 27) : kMaxPoints) || n_ref > (pred ? (1 << 27) : kMaxPoints))
+  if (n > Coder::kMaxN || n_ref > Coder::kMaxN)
     return fail(GPCC_ERR_INVALID_ARG, "too many points per call");
-  if ((lift ? lift->num_qp_regions : pred->num_qp_regions) != 0)
+  if (params->num_qp_regions != 0)
     return fail(GPCC_ERR_UNSUPPORTED, "inter prediction together with QP regions stays on the reference CPU path");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -4142,87 +3994,38 @@ rdo_attr_driver(
     pool_free(ctx, d_orig);
     pool_free(ctx, d_xyz);
   };
-  // the lifting transform reads the frame's attributes in fixed point (launch_lift)
-  std::vector<int64_t> a_frame;
-  if (lift) {
-    a_frame.resize((size_t)n_ref);
-    for (size_t t = 0; t < a_frame.size(); t++)
-      a_frame[t] = (int64_t)attrs_ref[t] * 256;  // << kFixedPointAttributeShift
-  }
+  const typename Coder::Frame frame = Coder::stage_frame(attrs_ref, (size_t)n_ref);
   auto candidate = [&](int k) -> int {
     const bool inter = k == 0;
     const int nf = inter ? n_ref : 0;
-    const size_t scratch_bytes = lift ? lift_scratch_bytes(n + nf, 1) : pred_scratch_bytes(n, nf);
-    // neighbour indices behind the frame, values, lcp / icp block, scratch (+ a 256-byte round-up each)
-    const size_t extra = N * 12 + N * 4 + scratch_bytes + 8 * 1024;
-    LodInterFrame frame{xyz_ref, n_ref, search_range, frame_distance};
+    // (one component: no side coefficients; the frame's neighbour indices only where there is a frame)
+    const unsigned what = (inter ? kBlkFrameNi : 0u) | kBlkValues;
+    LodInterFrame lod_frame{xyz_ref, n_ref, search_range, frame_distance};
     LodDeviceOut o;
-    int r = lod_build_core(ctx, inter ? lod_inter : lod_intra, xyz, n, extra, &o, false, inter ? &frame : nullptr, nullptr, d_xyz);
+    int r = lod_build_core(
+      ctx, inter ? lod_inter : lod_intra, xyz, n, slice_reserve<Coder>(n, 1, nf, what), &o, false,
+      inter ? &lod_frame : nullptr, nullptr, d_xyz);
     if (r)
       return r;
-    Arena ar = ctx->arena;  // carve behind the LoD workspace
-    ar.used = o.arena_end;
-    int32_t* d_ni = inter ? ar.take<int32_t>(N * 3) : nullptr;
-    int32_t* d_values = ar.take<int32_t>(N);
-    int8_t* d_side = ar.take<int8_t>(GPCC_MAX_LODS * 3);  // (last-component / inter-component coefficients: none with one component)
-    char* scratch = ar.base + ar.used;
-    if (ar.used + scratch_bytes > ctx->arena.cap)
-      return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
-    const int32_t* ni = o.neigh_index;
-    if (inter) {
-      Timer tm(ctx, "rdo_frame_neighbours");
-      hipLaunchKernelGGL(
-        rdo_frame_neighbours_kernel, dim3(grid_for((int64_t)N * 3, 256)), dim3(256), 0, st, n, o.count, o.inter_ref,
-        o.neigh_index, d_ni);
-      ni = d_ni;
-    }
-    HIP_TRY(hipMemcpyAsync(d_rec[k], d_orig, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
-    if (lift) {
-      gpcc_lift_params lp = *lift;
-      lp.scalable_lifting_enabled_flag = 0;
-      lp.last_component_prediction_enabled_flag = 0;
-      lp.num_lods = (int)o.npl.size();
-      for (size_t i = 0; i < o.npl.size(); i++)
-        lp.num_points_in_lod[i] = o.npl[i];
-      r = check_lift_params(&lp, n, 1);
-      if (r)
-        return r;
-      LiftDev d{};
-      d.nc = o.count;
-      d.ni = ni;
-      d.nw = o.weight;
-      d.indexes = o.indexes;
-      d.attrs = d_rec[k];
-      d.coeffs = d_values;
-      r = launch_lift<1>(ctx, true, &lp, n, d, d_side, scratch, nf, inter ? a_frame.data() : nullptr);
-    } else {
-      gpcc_pred_params pp = *pred;
-      pp.scalable_lifting_enabled_flag = 0;
-      pp.inter_component_prediction_enabled_flag = 0;
-      pp.num_lods = (int)o.npl.size();
-      for (size_t i = 0; i < o.npl.size(); i++)
-        pp.num_points_in_lod[i] = o.npl[i];
-      r = check_pred_params(&pp, n, 1, true);
-      if (r)
-        return r;
-      PredDev d{};
-      d.nc = o.count;
-      d.ni = ni;
-      d.nw = o.weight;
-      d.indexes = o.indexes;
-      d.attrs = d_rec[k];
-      d.values = d_values;
-      r = launch_pred<1>(ctx, true, &pp, n, d, d_side, scratch, nf, inter ? attrs_ref : nullptr);
-    }
-    if (r)
-      return r;  // (a predicting candidate that did not settle: pred_encoder_unsettled)
-    int32_t h_err = 0;
-    HIP_TRY(d2h_user(ctx, values + (size_t)k * N, d_values, sizeof(int32_t) * N, st));
-    HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h_err)
-      return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
-    return pred ? pred_check_error(ctx) : GPCC_OK;
+    typename Coder::Params p = *params;
+    return code_slice<Coder>(
+      ctx, true, false, &p, n, 1, o, what, nf, frame, nullptr,
+      [&](const SliceBlocks& b, LodCoderDev& d) -> int {
+        if (inter) {
+          Timer tm(ctx, "rdo_frame_neighbours");
+          hipLaunchKernelGGL(
+            rdo_frame_neighbours_kernel, dim3(grid_for((int64_t)N * 3, 256)), dim3(256), 0, st, n, o.count,
+            o.inter_ref, o.neigh_index, b.ni);
+          d.ni = b.ni;
+        }
+        HIP_TRY(hipMemcpyAsync(d_rec[k], d_orig, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
+        d.attrs = d_rec[k];
+        return GPCC_OK;
+      },
+      [&](const SliceBlocks& b) -> int {
+        HIP_TRY(d2h_user(ctx, values + (size_t)k * N, b.values, sizeof(int32_t) * N, st));
+        return GPCC_OK;
+      });
   };
   auto run = [&]() -> int {
     HIP_TRY(pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * N));
@@ -4265,7 +4068,6 @@ rdo_attr_driver(
   return r;
 }
 
-namespace {
 int
 slice_driver(
   gpcc_ctx* ctx, const gpcc_raht_params* params, bool encoder, const int32_t* xyz,
@@ -4323,7 +4125,7 @@ slice_driver(
     {
       const int saved = ctx->morton_bits;
       ctx->morton_bits = bits;
-      int r = gpcc_dev_attr_morton_sort_impl(ctx, 1, offs, d_xyz, d_m, d_order);
+      int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_m, d_order);
       ctx->morton_bits = saved;
       if (r)
         return r;
@@ -4416,61 +4218,9 @@ slice_driver(
   cleanup();
   return r;
 }
-}  // namespace
 
-static int
-gpcc_raht_encode_attr_packed_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const int32_t* xyz, int32_t* attrs,
-  int32_t* runs, int32_t* values, int32_t* num_symbols, int32_t* trailing_run, int32_t n,
-  int32_t c, int32_t bitdepth)
-{
-  if (!runs)
-    return fail(GPCC_ERR_INVALID_ARG, "runs is null");
-  return slice_driver(
-    ctx, params, true, xyz, attrs, nullptr, n, c, bitdepth, runs, values, num_symbols, trailing_run);
-}
-
-static int
-gpcc_raht_encode_attr_packed_regions_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, const int32_t* xyz,
-  int32_t* attrs, int32_t* runs, int32_t* values, int32_t* num_symbols, int32_t* trailing_run, int32_t n,
-  int32_t c, int32_t bitdepth)
-{
-  if (!runs)
-    return fail(GPCC_ERR_INVALID_ARG, "runs is null");
-  return slice_driver(
-    ctx, params, true, xyz, attrs, nullptr, n, c, bitdepth, runs, values, num_symbols, trailing_run, regions);
-}
-
-static int
-gpcc_raht_decode_attr_regions_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, const int32_t* xyz,
-  int32_t* attrs, const int32_t* coeffs, int32_t n, int32_t c, int32_t bitdepth)
-{
-  return slice_driver(
-    ctx, params, false, xyz, attrs, const_cast<int32_t*>(coeffs), n, c, bitdepth, nullptr, nullptr, nullptr,
-    nullptr, regions);
-}
-
-static int
-gpcc_raht_encode_attr_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const int32_t* xyz,
-  int32_t* attrs, int32_t* coeffs, int32_t n, int32_t c, int32_t bitdepth)
-{
-  return slice_driver(ctx, params, true, xyz, attrs, coeffs, n, c, bitdepth);
-}
-
-static int
-gpcc_raht_decode_attr_impl(
-  gpcc_ctx* ctx, const gpcc_raht_params* params, const int32_t* xyz,
-  int32_t* attrs, const int32_t* coeffs, int32_t n, int32_t c, int32_t bitdepth)
-{
-  return slice_driver(
-    ctx, params, false, xyz, attrs, const_cast<int32_t*>(coeffs), n, c, bitdepth);
-}
-
-static int
-gpcc_zero_run_pack_impl(
+int
+zero_run_pack(
   gpcc_ctx* ctx, const int32_t* coeffs, int32_t n, int32_t c, int32_t planar,
   int32_t* runs, int32_t* values, int32_t* num_symbols, int32_t* trailing_run)
 {
@@ -4529,8 +4279,8 @@ gpcc_zero_run_pack_impl(
   return GPCC_OK;
 }
 
-static int
-gpcc_estimate_dist2_impl(
+int
+estimate_dist2(
   gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int32_t sampling_period,
   int32_t search_range, float percentile, int32_t* shift_bits)
 {
@@ -4585,7 +4335,7 @@ gpcc_estimate_dist2_impl(
   return rc;
 }
 
-}  // extern "C"
+}  // namespace
 
 #if GPCC_FIN_VAR == 2
 extern "C" int
@@ -4682,6 +4432,13 @@ counted(gpcc_ctx* ctx, int rc, int64_t points)
   return rc;
 }
 
+// the points of a batch, for counted()
+static int64_t
+batch_points(const int64_t* offsets, int32_t num_slices)
+{
+  return offsets && num_slices > 0 ? offsets[num_slices] : 0;
+}
+
 extern "C" {
 
 int
@@ -4689,7 +4446,7 @@ gpcc_raht_forward(
   gpcc_ctx* ctx, const gpcc_raht_params* params, const int64_t* morton,
   const int32_t* qp_off, int32_t* attrs, int32_t* coeffs, int32_t n, int32_t c)
 {
-  return counted(ctx, gpcc_raht_forward_impl(ctx, params, morton, qp_off, attrs, coeffs, n, c), n);
+  return counted(ctx, host_transform(ctx, params, true, morton, qp_off, attrs, coeffs, n, c), n);
 }
 
 int
@@ -4698,7 +4455,7 @@ gpcc_raht_inverse(
   const int32_t* qp_off, int32_t* attrs, const int32_t* coeffs, int32_t n,
   int32_t c)
 {
-  return counted(ctx, gpcc_raht_inverse_impl(ctx, params, morton, qp_off, attrs, coeffs, n, c), n);
+  return counted(ctx, host_transform(ctx, params, false, morton, qp_off, attrs, const_cast<int32_t*>(coeffs), n, c), n);
 }
 
 int
@@ -4742,7 +4499,11 @@ gpcc_dev_raht_forward(
   const int64_t* offsets, const void* d_morton, const void* d_qp_off,
   void* d_attrs, void* d_coeffs, int32_t c)
 {
-  return counted(ctx, gpcc_dev_raht_forward_impl(ctx, params, num_slices, offsets, d_morton, d_qp_off, d_attrs, d_coeffs, c), (offsets && num_slices > 0 ? offsets[num_slices] : 0));
+  return counted(
+    ctx,
+    dev_transform(
+      ctx, params, true, num_slices, offsets, d_morton, d_qp_off, d_attrs, d_coeffs, c, ctx ? ctx->morton_bits : 0),
+    batch_points(offsets, num_slices));
 }
 
 int
@@ -4751,7 +4512,12 @@ gpcc_dev_raht_inverse(
   const int64_t* offsets, const void* d_morton, const void* d_qp_off,
   void* d_attrs, const void* d_coeffs, int32_t c)
 {
-  return counted(ctx, gpcc_dev_raht_inverse_impl(ctx, params, num_slices, offsets, d_morton, d_qp_off, d_attrs, d_coeffs, c), (offsets && num_slices > 0 ? offsets[num_slices] : 0));
+  return counted(
+    ctx,
+    dev_transform(
+      ctx, params, false, num_slices, offsets, d_morton, d_qp_off, d_attrs, const_cast<void*>(d_coeffs), c,
+      ctx ? ctx->morton_bits : 0),
+    batch_points(offsets, num_slices));
 }
 
 int
@@ -4759,14 +4525,14 @@ gpcc_dev_attr_morton_sort(
   gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz,
   void* d_morton, void* d_order)
 {
-  return counted(ctx, gpcc_dev_attr_morton_sort_impl(ctx, num_slices, offsets, d_xyz, d_morton, d_order), (offsets && num_slices > 0 ? offsets[num_slices] : 0));
+  return counted(ctx, dev_morton_sort(ctx, num_slices, offsets, d_xyz, d_morton, d_order), batch_points(offsets, num_slices));
 }
 
 int
 gpcc_attr_morton_sort(
   gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int64_t* morton, int32_t* order)
 {
-  return counted(ctx, gpcc_attr_morton_sort_impl(ctx, xyz, n, morton, order), n);
+  return counted(ctx, host_morton_sort(ctx, xyz, n, morton, order), n);
 }
 
 int
@@ -4776,7 +4542,11 @@ gpcc_lift_forward(
   const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off,
   int32_t* attrs, int32_t* coeffs, int8_t* lcp_coeffs)
 {
-  return counted(ctx, gpcc_lift_forward_impl(ctx, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, coeffs, lcp_coeffs), n);
+  return counted(
+    ctx,
+    host_lod_coder<LiftCoder>(
+      ctx, true, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, coeffs, lcp_coeffs),
+    n);
 }
 
 int
@@ -4786,7 +4556,12 @@ gpcc_lift_inverse(
   const int32_t* neigh_weight, const int32_t* indexes, const int32_t* qp_off,
   int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs)
 {
-  return counted(ctx, gpcc_lift_inverse_impl(ctx, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, coeffs, lcp_coeffs), n);
+  return counted(
+    ctx,
+    host_lod_coder<LiftCoder>(
+      ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs,
+      const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs)),
+    n);
 }
 
 int
@@ -4799,7 +4574,7 @@ gpcc_lift_forward_inter(
     return counted(ctx, fail(GPCC_ERR_INVALID_ARG, "inter_ref is null"), n);
   return counted(
     ctx,
-    host_lift(
+    host_lod_coder<LiftCoder>(
       ctx, true, params, n, 1, neigh_count, neigh_index, neigh_weight, indexes, nullptr, attrs, coeffs,
       nullptr, inter_ref, attrs_ref, n_ref),
     n);
@@ -4816,7 +4591,7 @@ gpcc_lift_inverse_inter(
     return counted(ctx, fail(GPCC_ERR_INVALID_ARG, "inter_ref is null"), n);
   return counted(
     ctx,
-    host_lift(
+    host_lod_coder<LiftCoder>(
       ctx, false, params, n, 1, neigh_count, neigh_index, neigh_weight, indexes, nullptr, attrs,
       const_cast<int32_t*>(coeffs), nullptr, inter_ref, attrs_ref, n_ref),
     n);
@@ -4832,7 +4607,7 @@ gpcc_pred_forward_inter(
     return counted(ctx, fail(GPCC_ERR_INVALID_ARG, "inter_ref is null"), n);
   return counted(
     ctx,
-    host_pred(
+    host_lod_coder<PredCoder>(
       ctx, true, params, n, 1, neigh_count, neigh_index, neigh_weight, indexes, nullptr, attrs, values,
       nullptr, inter_ref, attrs_ref, n_ref),
     n);
@@ -4849,7 +4624,7 @@ gpcc_pred_inverse_inter(
     return counted(ctx, fail(GPCC_ERR_INVALID_ARG, "inter_ref is null"), n);
   return counted(
     ctx,
-    host_pred(
+    host_lod_coder<PredCoder>(
       ctx, false, params, n, 1, neigh_count, neigh_index, neigh_weight, indexes, nullptr, attrs,
       const_cast<int32_t*>(values), nullptr, inter_ref, attrs_ref, n_ref),
     n);
@@ -4860,7 +4635,7 @@ gpcc_lod_compute_weights(
   gpcc_ctx* ctx, int32_t n, int32_t* neigh_count, const uint64_t* dist2,
   int32_t* neigh_weight)
 {
-  return counted(ctx, gpcc_lod_compute_weights_impl(ctx, n, neigh_count, dist2, neigh_weight), n);
+  return counted(ctx, lod_compute_weights(ctx, n, neigh_count, dist2, neigh_weight), n);
 }
 
 int
@@ -4869,7 +4644,7 @@ gpcc_lod_build(
   int32_t* neigh_count, int32_t* neigh_index, int32_t* neigh_weight,
   int32_t* indexes, int32_t* num_points_in_lod, int32_t* num_lods)
 {
-  return counted(ctx, gpcc_lod_build_impl(ctx, lp, xyz, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods), n);
+  return counted(ctx, lod_build(ctx, lp, xyz, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods), n);
 }
 
 int
@@ -4886,7 +4661,7 @@ gpcc_lod_build_partial(
     if (rc)
       return counted(ctx, rc, n);
   }
-  return counted(ctx, gpcc_lod_build_impl(ctx, lp, xyz, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods, &pd), n);
+  return counted(ctx, lod_build(ctx, lp, xyz, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods, &pd), n);
 }
 
 int
@@ -4896,13 +4671,18 @@ gpcc_lift_inverse_partial(
   const int32_t* neigh_index, const int32_t* neigh_weight, const int32_t* indexes,
   const int32_t* qp_off, int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs)
 {
+  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
   if (params && n > 0) {
-    const int rc = check_partial(
-      PartialDecode{min_geom_node_size_log2, geom_num_points}, n, params->scalable_lifting_enabled_flag != 0, 2, false);
+    const int rc = check_partial(pd, n, params->scalable_lifting_enabled_flag != 0, 2, false);
     if (rc)
       return counted(ctx, rc, n);
   }
-  return counted(ctx, gpcc_lift_inverse_partial_impl(ctx, params, n, c, min_geom_node_size_log2, geom_num_points, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, coeffs, lcp_coeffs), n);
+  return counted(
+    ctx,
+    host_lod_coder<LiftCoder>(
+      ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs,
+      const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs), nullptr, nullptr, 0, &pd),
+    n);
 }
 
 int
@@ -4911,14 +4691,18 @@ gpcc_lift_decode_attr_partial(
   int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs, int32_t* indexes, int32_t n,
   int32_t c, int32_t min_geom_node_size_log2, int32_t geom_num_points)
 {
+  const PartialDecode pd{min_geom_node_size_log2, geom_num_points};
   if (lod && n > 0) {
-    const int rc = check_partial(
-      PartialDecode{min_geom_node_size_log2, geom_num_points}, n, lod->scalable_lifting_enabled_flag != 0,
-      lod->attr_encoding, false);
+    const int rc = check_partial(pd, n, lod->scalable_lifting_enabled_flag != 0, lod->attr_encoding, false);
     if (rc)
       return counted(ctx, rc, n);
   }
-  return counted(ctx, gpcc_lift_decode_attr_partial_impl(ctx, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c, min_geom_node_size_log2, geom_num_points), n);
+  return counted(
+    ctx,
+    slice_attr_driver<LiftCoder>(
+      ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs), indexes, n,
+      c, &pd),
+    n);
 }
 
 int
@@ -4935,8 +4719,8 @@ gpcc_lift_encode_attr_rdo(
     return counted(ctx, rc, n);
   return counted(
     ctx,
-    rdo_attr_driver(
-      ctx, lod_inter, lod_intra, lift, nullptr, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range,
+    rdo_attr_driver<LiftCoder>(
+      ctx, lod_inter, lod_intra, lift, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range,
       frame_distance, values, recon, dist),
     n);
 }
@@ -4954,8 +4738,8 @@ gpcc_pred_encode_attr_rdo(
     return counted(ctx, rc, n);
   return counted(
     ctx,
-    rdo_attr_driver(
-      ctx, lod_inter, lod_intra, nullptr, pred, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range,
+    rdo_attr_driver<PredCoder>(
+      ctx, lod_inter, lod_intra, pred, xyz, attrs, n, xyz_ref, attrs_ref, n_ref, search_range,
       frame_distance, values, recon, dist),
     n);
 }
@@ -4995,7 +4779,7 @@ gpcc_lod_build_inter(
 {
   return counted(
     ctx,
-    gpcc_lod_build_inter_impl(
+    lod_build_inter(
       ctx, lp, xyz, n, xyz_ref, n_ref, search_range, frame_distance, neigh_count, neigh_index,
       neigh_weight, indexes, num_points_in_lod, num_lods, inter_ref),
     n);
@@ -5006,7 +4790,7 @@ gpcc_lift_encode_attr(
   gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
   int32_t* attrs, int32_t* coeffs, int8_t* lcp_coeffs, int32_t* indexes, int32_t n, int32_t c)
 {
-  return counted(ctx, gpcc_lift_encode_attr_impl(ctx, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c), n);
+  return counted(ctx, slice_attr_driver<LiftCoder>(ctx, true, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c), n);
 }
 
 int
@@ -5015,7 +4799,11 @@ gpcc_lift_decode_attr(
   int32_t* attrs, const int32_t* coeffs, const int8_t* lcp_coeffs, int32_t* indexes, int32_t n,
   int32_t c)
 {
-  return counted(ctx, gpcc_lift_decode_attr_impl(ctx, lod, lift, xyz, attrs, coeffs, lcp_coeffs, indexes, n, c), n);
+  return counted(
+    ctx,
+    slice_attr_driver<LiftCoder>(
+      ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs), const_cast<int8_t*>(lcp_coeffs), indexes, n, c),
+    n);
 }
 
 int
@@ -5025,7 +4813,7 @@ gpcc_pred_forward(
   const int32_t* indexes, const int32_t* qp_off, int32_t* attrs, int32_t* values,
   int8_t* icp_coeffs)
 {
-  return counted(ctx, host_pred(ctx, true, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, values, icp_coeffs), n);
+  return counted(ctx, host_lod_coder<PredCoder>(ctx, true, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, values, icp_coeffs), n);
 }
 
 int
@@ -5035,7 +4823,7 @@ gpcc_pred_inverse(
   const int32_t* indexes, const int32_t* qp_off, int32_t* attrs, const int32_t* values,
   const int8_t* icp_coeffs)
 {
-  return counted(ctx, host_pred(ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, const_cast<int32_t*>(values), const_cast<int8_t*>(icp_coeffs)), n);
+  return counted(ctx, host_lod_coder<PredCoder>(ctx, false, params, n, c, neigh_count, neigh_index, neigh_weight, indexes, qp_off, attrs, const_cast<int32_t*>(values), const_cast<int8_t*>(icp_coeffs)), n);
 }
 
 int
@@ -5043,7 +4831,7 @@ gpcc_pred_encode_attr(
   gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, const int32_t* xyz,
   int32_t* attrs, int32_t* values, int8_t* icp_coeffs, int32_t* indexes, int32_t n, int32_t c)
 {
-  return counted(ctx, pred_attr_driver(ctx, true, lod, pred, xyz, attrs, values, icp_coeffs, indexes, n, c), n);
+  return counted(ctx, slice_attr_driver<PredCoder>(ctx, true, lod, pred, xyz, attrs, values, icp_coeffs, indexes, n, c), n);
 }
 
 int
@@ -5052,7 +4840,7 @@ gpcc_pred_decode_attr(
   int32_t* attrs, const int32_t* values, const int8_t* icp_coeffs, int32_t* indexes, int32_t n,
   int32_t c)
 {
-  return counted(ctx, pred_attr_driver(ctx, false, lod, pred, xyz, attrs, const_cast<int32_t*>(values), const_cast<int8_t*>(icp_coeffs), indexes, n, c), n);
+  return counted(ctx, slice_attr_driver<PredCoder>(ctx, false, lod, pred, xyz, attrs, const_cast<int32_t*>(values), const_cast<int8_t*>(icp_coeffs), indexes, n, c), n);
 }
 
 int
@@ -5061,7 +4849,11 @@ gpcc_raht_encode_attr_packed(
   int32_t* runs, int32_t* values, int32_t* num_symbols, int32_t* trailing_run, int32_t n,
   int32_t c, int32_t bitdepth)
 {
-  return counted(ctx, gpcc_raht_encode_attr_packed_impl(ctx, params, xyz, attrs, runs, values, num_symbols, trailing_run, n, c, bitdepth), n);
+  if (!runs)
+    return counted(ctx, fail(GPCC_ERR_INVALID_ARG, "runs is null"), n);
+  return counted(
+    ctx,
+    slice_driver(ctx, params, true, xyz, attrs, nullptr, n, c, bitdepth, runs, values, num_symbols, trailing_run), n);
 }
 
 int
@@ -5069,7 +4861,7 @@ gpcc_raht_encode_attr(
   gpcc_ctx* ctx, const gpcc_raht_params* params, const int32_t* xyz,
   int32_t* attrs, int32_t* coeffs, int32_t n, int32_t c, int32_t bitdepth)
 {
-  return counted(ctx, gpcc_raht_encode_attr_impl(ctx, params, xyz, attrs, coeffs, n, c, bitdepth), n);
+  return counted(ctx, slice_driver(ctx, params, true, xyz, attrs, coeffs, n, c, bitdepth), n);
 }
 
 int
@@ -5077,7 +4869,7 @@ gpcc_raht_decode_attr(
   gpcc_ctx* ctx, const gpcc_raht_params* params, const int32_t* xyz,
   int32_t* attrs, const int32_t* coeffs, int32_t n, int32_t c, int32_t bitdepth)
 {
-  return counted(ctx, gpcc_raht_decode_attr_impl(ctx, params, xyz, attrs, coeffs, n, c, bitdepth), n);
+  return counted(ctx, slice_driver(ctx, params, false, xyz, attrs, const_cast<int32_t*>(coeffs), n, c, bitdepth), n);
 }
 
 int
@@ -5086,10 +4878,12 @@ gpcc_raht_encode_attr_packed_regions(
   int32_t* attrs, int32_t* runs, int32_t* values, int32_t* num_symbols, int32_t* trailing_run, int32_t n,
   int32_t c, int32_t bitdepth)
 {
+  if (!runs)
+    return counted(ctx, fail(GPCC_ERR_INVALID_ARG, "runs is null"), n);
   return counted(
     ctx,
-    gpcc_raht_encode_attr_packed_regions_impl(
-      ctx, params, regions, xyz, attrs, runs, values, num_symbols, trailing_run, n, c, bitdepth),
+    slice_driver(
+      ctx, params, true, xyz, attrs, nullptr, n, c, bitdepth, runs, values, num_symbols, trailing_run, regions),
     n);
 }
 
@@ -5098,7 +4892,12 @@ gpcc_raht_decode_attr_regions(
   gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, const int32_t* xyz,
   int32_t* attrs, const int32_t* coeffs, int32_t n, int32_t c, int32_t bitdepth)
 {
-  return counted(ctx, gpcc_raht_decode_attr_regions_impl(ctx, params, regions, xyz, attrs, coeffs, n, c, bitdepth), n);
+  return counted(
+    ctx,
+    slice_driver(
+      ctx, params, false, xyz, attrs, const_cast<int32_t*>(coeffs), n, c, bitdepth, nullptr, nullptr, nullptr, nullptr,
+      regions),
+    n);
 }
 
 int
@@ -5106,7 +4905,7 @@ gpcc_zero_run_pack(
   gpcc_ctx* ctx, const int32_t* coeffs, int32_t n, int32_t c, int32_t planar,
   int32_t* runs, int32_t* values, int32_t* num_symbols, int32_t* trailing_run)
 {
-  return counted(ctx, gpcc_zero_run_pack_impl(ctx, coeffs, n, c, planar, runs, values, num_symbols, trailing_run), n);
+  return counted(ctx, zero_run_pack(ctx, coeffs, n, c, planar, runs, values, num_symbols, trailing_run), n);
 }
 
 int
@@ -5114,7 +4913,7 @@ gpcc_estimate_dist2(
   gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int32_t sampling_period,
   int32_t search_range, float percentile, int32_t* shift_bits)
 {
-  return counted(ctx, gpcc_estimate_dist2_impl(ctx, xyz, n, sampling_period, search_range, percentile, shift_bits), n);
+  return counted(ctx, estimate_dist2(ctx, xyz, n, sampling_period, search_range, percentile, shift_bits), n);
 }
 
 }  // extern "C"
@@ -5239,17 +5038,6 @@ check_slices(gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets)
 }
 
 int
-lod_error_word(gpcc_ctx* ctx, const LodDeviceOut& o)
-{
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (h_err)
-    return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
-  return GPCC_OK;
-}
-
-int
 dev_lod_build(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, int32_t num_slices, const int64_t* offsets,
   const int32_t* d_xyz, int32_t* d_count, int32_t* d_index, int32_t* d_weight,
@@ -5281,151 +5069,60 @@ dev_lod_build(
   });
 }
 
+// Device tier: slices back to back in HBM, attributes and values in the caller's buffers, in place.
+// `side`: host memory, kSideBytes per slice.  Partial decode (null: whole slices; lifting only): one first
+// level for the batch, the slices' full point counts.
+template<class Coder>
 int
-dev_lift_attr(
-  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, gpcc_lift_params* lift,
-  int32_t num_slices, const int64_t* offsets, const int32_t* d_xyz, int32_t* d_attrs,
-  int32_t* d_coeffs, int8_t* lcp, int32_t* d_indexes, int32_t c,
-  // partial decode (null: whole slices): one first level for the batch, the slices' full point counts
-  const int32_t* min_geom_node_size_log2 = nullptr, const int32_t* geom_num_points = nullptr)
+dev_lod_coder_attr(
+  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, typename Coder::Params* params, int32_t num_slices,
+  const int64_t* offsets, const int32_t* d_xyz, int32_t* d_attrs, int32_t* d_values, int8_t* side,
+  int32_t* d_indexes, int32_t c, const int32_t* min_geom_node_size_log2 = nullptr,
+  const int32_t* geom_num_points = nullptr)
 {
   int r = check_slices(ctx, num_slices, offsets);
   if (r)
     return r;
-  if (!lift || !d_xyz || !d_attrs || !d_coeffs || c < 1 || c > 3)
-    return fail(GPCC_ERR_INVALID_ARG, "null buffer or attribute count not 1..3");
-  if (min_geom_node_size_log2) {
-    if (!lod || !geom_num_points)
-      return fail(GPCC_ERR_INVALID_ARG, "null buffer");
-    // (the scalars themselves: checked by the entry, and again per slice by lod_build_core)
-  }
+  if (!params || !d_xyz || !d_attrs || !d_values || !Coder::count_ok(c))
+    return fail(GPCC_ERR_INVALID_ARG, Coder::kBadCount);
+  // (the scalars of a partial decode: checked by the entry, and again per slice by lod_build_core)
+  if (min_geom_node_size_log2 && (!lod || !geom_num_points))
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
   for (int s = 0; s < num_slices; s++)
-    if (c == 3 && lift[s].last_component_prediction_enabled_flag && !lcp)
-      return fail(GPCC_ERR_INVALID_ARG, "lcp_coeffs is null");
+    if (Coder::side_on(params[s], c) && !side)
+      return fail(GPCC_ERR_INVALID_ARG, Coder::kSideNull);
   return run_slices(ctx, num_slices, [&](gpcc_ctx* lane, int s) -> int {
     hipStream_t st = lane->stream;
-    int r = GPCC_OK;
-    gpcc_lift_params* lf = lift + s;
-    const bool lcp_on = c == 3 && lf->last_component_prediction_enabled_flag;
-    const size_t b = (size_t)offsets[s], N = (size_t)(offsets[s + 1] - offsets[s]);
+    typename Coder::Params* p = params + s;
+    const bool side_on = Coder::side_on(*p, c);
+    const size_t first = (size_t)offsets[s], N = (size_t)(offsets[s + 1] - offsets[s]);
     const int32_t n = (int32_t)N;
-    const size_t extra = 512 + lift_scratch_bytes(n, c) + 1024 + N * 8 + 256;
-    LodDeviceOut o;
     PartialDecode pd{0, n};
     if (min_geom_node_size_log2)
       pd = PartialDecode{*min_geom_node_size_log2, geom_num_points[s]};
     const PartialDecode* partial = min_geom_node_size_log2 ? &pd : nullptr;
-    r = lod_build_core(lane, lod, d_xyz + 3 * b, n, extra, &o, true, nullptr, partial);
-    if (r)
-      return r;
-    lf->scalable_lifting_enabled_flag = lod->scalable_lifting_enabled_flag != 0;
-    lf->num_lods = (int)o.npl.size();
-    for (size_t i = 0; i < o.npl.size(); i++)
-      lf->num_points_in_lod[i] = o.npl[i];
-    r = check_lift_params(lf, n, c);
-    if (r)
-      return r;
-    Arena ar = lane->arena;  // carve behind the LoD workspace
-    ar.used = o.arena_end;
-    LiftDev d{};
-    d.nc = o.count;
-    d.ni = o.neigh_index;
-    d.nw = o.weight;
-    d.indexes = o.indexes;
-    r = qp_regions_to_points(lf, o.xyz, n, ar.take<int32_t>(N * 2), st, &d.qp_off);
-    if (r)
-      return r;
-    d.attrs = d_attrs + b * c;    // the caller's buffers, in place
-    d.coeffs = d_coeffs + b * c;
-    int8_t* d_lcp = ar.take<int8_t>(GPCC_MAX_LODS);
-    char* scratch = ar.base + ar.used;
-    if (ar.used + lift_scratch_bytes(n, c) > lane->arena.cap)
-      return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
-    int8_t* h_lcp = lcp ? lcp + (size_t)s * GPCC_MAX_LODS : nullptr;
-    if (!encoder && lcp_on)
-      HIP_TRY(hipMemcpyAsync(d_lcp, h_lcp, GPCC_MAX_LODS, hipMemcpyHostToDevice, st));
-    switch (c) {
-    case 1: r = launch_lift<1>(lane, encoder, lf, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-    case 2: r = launch_lift<2>(lane, encoder, lf, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-    default: r = launch_lift<3>(lane, encoder, lf, n, d, d_lcp, scratch, 0, nullptr, partial); break;
-    }
-    if (r)
-      return r;
-    if (encoder && lcp_on)
-      HIP_TRY(hipMemcpyAsync(h_lcp, d_lcp, GPCC_MAX_LODS, hipMemcpyDeviceToHost, st));
-    if (d_indexes)
-      HIP_TRY(hipMemcpyAsync(d_indexes + b, o.indexes, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
-    r = lod_error_word(lane, o);
-    if (r)
-      return r;
-    return GPCC_OK;
-  });
-}
-
-int
-dev_pred_attr(
-  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, gpcc_pred_params* pred,
-  int32_t num_slices, const int64_t* offsets, const int32_t* d_xyz, int32_t* d_attrs,
-  int32_t* d_values, int8_t* icp, int32_t* d_indexes, int32_t c)
-{
-  int r = check_slices(ctx, num_slices, offsets);
-  if (r)
-    return r;
-  if (!pred || !d_xyz || !d_attrs || !d_values || (c != 1 && c != 3))
-    return fail(GPCC_ERR_INVALID_ARG, "null buffer or attribute count not 1 / 3");
-  for (int s = 0; s < num_slices; s++) {
-    if (c == 3 && pred[s].inter_component_prediction_enabled_flag && !icp)
-      return fail(GPCC_ERR_INVALID_ARG, "icp_coeffs is null");
-  }
-  return run_slices(ctx, num_slices, [&](gpcc_ctx* lane, int s) -> int {
-    hipStream_t st = lane->stream;
-    gpcc_pred_params* pp = pred + s;
-    const bool icp_on = c == 3 && pp->inter_component_prediction_enabled_flag;
-    const size_t b = (size_t)offsets[s], N = (size_t)(offsets[s + 1] - offsets[s]);
-    const int32_t n = (int32_t)N;
-    const size_t extra = 1024 + pred_scratch_bytes(n) + 1024 + N * 8 + 256;
     LodDeviceOut o;
-    int r = lod_build_core(lane, lod, d_xyz + 3 * b, n, extra, &o, true);
+    int r = lod_build_core(
+      lane, lod, d_xyz + 3 * first, n, slice_reserve<Coder>(n, c, 0, kBlkQp), &o, true, nullptr, partial);
     if (r)
       return r;
-    pp->scalable_lifting_enabled_flag = lod->scalable_lifting_enabled_flag != 0;
-    pp->num_lods = (int)o.npl.size();
-    for (size_t i = 0; i < o.npl.size(); i++)
-      pp->num_points_in_lod[i] = o.npl[i];
-    r = check_pred_params(pp, n, c, encoder);
-    if (r)
-      return r;
-    Arena ar = lane->arena;  // carve behind the LoD workspace
-    ar.used = o.arena_end;
-    PredDev d{};
-    d.nc = o.count;
-    d.ni = o.neigh_index;
-    d.nw = o.weight;
-    d.indexes = o.indexes;
-    r = qp_regions_to_points(pp, o.xyz, n, ar.take<int32_t>(N * 2), st, &d.qp_off);
-    if (r)
-      return r;
-    d.attrs = d_attrs + b * c;  // the caller's buffers, in place
-    d.values = d_values + b * c;
-    int8_t* d_icp = ar.take<int8_t>(GPCC_MAX_LODS * 3);
-    char* scratch = ar.base + ar.used;
-    if (ar.used + pred_scratch_bytes(n) > lane->arena.cap)
-      return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
-    int8_t* h_icp = icp ? icp + (size_t)s * GPCC_MAX_LODS * 3 : nullptr;
-    if (!encoder && icp_on)
-      HIP_TRY(hipMemcpyAsync(d_icp, h_icp, GPCC_MAX_LODS * 3, hipMemcpyHostToDevice, st));
-    r = c == 1 ? launch_pred<1>(lane, encoder, pp, n, d, d_icp, scratch)
-               : launch_pred<3>(lane, encoder, pp, n, d, d_icp, scratch);
-    if (r)
-      return r;
-    if (encoder && icp_on)
-      HIP_TRY(hipMemcpyAsync(h_icp, d_icp, GPCC_MAX_LODS * 3, hipMemcpyDeviceToHost, st));
-    if (d_indexes)
-      HIP_TRY(hipMemcpyAsync(d_indexes + b, o.indexes, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
-    r = lod_error_word(lane, o);
-    if (r)
-      return r;
-    return pred_check_error(lane);
+    int8_t* h_side = side ? side + (size_t)s * Coder::kSideBytes : nullptr;
+    return code_slice<Coder>(
+      lane, encoder, lod->scalable_lifting_enabled_flag != 0, p, n, c, o, kBlkQp, 0, {}, partial,
+      [&](const SliceBlocks& b, LodCoderDev& d) -> int {
+        d.attrs = d_attrs + first * c;
+        d.values = d_values + first * c;
+        if (!encoder && side_on)
+          HIP_TRY(hipMemcpyAsync(b.side, h_side, Coder::kSideBytes, hipMemcpyHostToDevice, st));
+        return GPCC_OK;
+      },
+      [&](const SliceBlocks& b) -> int {
+        if (encoder && side_on)
+          HIP_TRY(hipMemcpyAsync(h_side, b.side, Coder::kSideBytes, hipMemcpyDeviceToHost, st));
+        if (d_indexes)
+          HIP_TRY(hipMemcpyAsync(d_indexes + first, o.indexes, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
+        return GPCC_OK;
+      });
   });
 }
 
@@ -5445,7 +5142,7 @@ gpcc_dev_lod_build(
       ctx, params, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_neigh_count,
       (int32_t*)d_neigh_index, (int32_t*)d_neigh_weight, (int32_t*)d_indexes,
       num_points_in_lod, num_lods),
-    offsets && num_slices > 0 ? offsets[num_slices] : 0);
+    batch_points(offsets, num_slices));
 }
 
 int
@@ -5456,10 +5153,10 @@ gpcc_dev_lift_encode_attr(
 {
   return counted(
     ctx,
-    dev_lift_attr(
+    dev_lod_coder_attr<LiftCoder>(
       ctx, true, lod, lift, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
       (int32_t*)d_coeffs, lcp_coeffs, (int32_t*)d_indexes, c),
-    offsets && num_slices > 0 ? offsets[num_slices] : 0);
+    batch_points(offsets, num_slices));
 }
 
 int
@@ -5470,11 +5167,11 @@ gpcc_dev_lift_decode_attr(
 {
   return counted(
     ctx,
-    dev_lift_attr(
+    dev_lod_coder_attr<LiftCoder>(
       ctx, false, lod, lift, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
       (int32_t*)const_cast<void*>(d_coeffs), const_cast<int8_t*>(lcp_coeffs),
       (int32_t*)d_indexes, c),
-    offsets && num_slices > 0 ? offsets[num_slices] : 0);
+    batch_points(offsets, num_slices));
 }
 
 int
@@ -5484,7 +5181,7 @@ gpcc_dev_lift_decode_attr_partial(
   const int8_t* lcp_coeffs, void* d_indexes, int32_t c, int32_t min_geom_node_size_log2,
   const int32_t* geom_num_points)
 {
-  const int64_t total = offsets && num_slices > 0 ? offsets[num_slices] : 0;
+  const int64_t total = batch_points(offsets, num_slices);
   if (lod && offsets && geom_num_points)
     for (int s = 0; s < num_slices; s++) {
       const int rc = check_partial(
@@ -5495,7 +5192,7 @@ gpcc_dev_lift_decode_attr_partial(
     }
   return counted(
     ctx,
-    dev_lift_attr(
+    dev_lod_coder_attr<LiftCoder>(
       ctx, false, lod, lift, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
       (int32_t*)const_cast<void*>(d_coeffs), const_cast<int8_t*>(lcp_coeffs),
       (int32_t*)d_indexes, c, &min_geom_node_size_log2, geom_num_points),
@@ -5510,10 +5207,10 @@ gpcc_dev_pred_encode_attr(
 {
   return counted(
     ctx,
-    dev_pred_attr(
+    dev_lod_coder_attr<PredCoder>(
       ctx, true, lod, pred, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
       (int32_t*)d_values, icp_coeffs, (int32_t*)d_indexes, c),
-    offsets && num_slices > 0 ? offsets[num_slices] : 0);
+    batch_points(offsets, num_slices));
 }
 
 int
@@ -5524,11 +5221,11 @@ gpcc_dev_pred_decode_attr(
 {
   return counted(
     ctx,
-    dev_pred_attr(
+    dev_lod_coder_attr<PredCoder>(
       ctx, false, lod, pred, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
       (int32_t*)const_cast<void*>(d_values), const_cast<int8_t*>(icp_coeffs),
       (int32_t*)d_indexes, c),
-    offsets && num_slices > 0 ? offsets[num_slices] : 0);
+    batch_points(offsets, num_slices));
 }
 
 }  // extern "C"
@@ -6096,14 +5793,6 @@ gpcc_binarise_symbols(
 
 // ---- attribute transfer onto a re-quantised geometry (recolour_kernels.hpp) -----------
 namespace {
-
-// inclusive scan of a[0 .. n) in place
-int
-rc_scan(gpcc_ctx* ctx, int32_t* a, size_t n, long long* sums)
-{
-  HIP_TRY(kd_scan(ctx->stream, a, n, sums));
-  return GPCC_OK;
-}
 
 // the working set of one tree's build, from the context's pool (recolour_kdtree.hpp)
 struct KdAlloc {

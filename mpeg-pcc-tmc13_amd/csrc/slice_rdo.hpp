@@ -107,7 +107,7 @@ slice_distortion_kernel(SliceDistArgs a)
 // The inter candidate's structure as the transforms read it: a neighbour that lives in the
 // reference frame is addressed BEHIND the n predictors (launch_lift / launch_pred: entry n + r
 // holds the frame's attribute r).  gpcc_lod_build_inter hands out the frame's own index and the
-// flag; the host entries add n on the host (host_lift / host_pred), this does it where the
+// flag; the host entries add n on the host (frame_neighbours_behind), this does it where the
 // structure is.
 __global__ __launch_bounds__(256) void
 rdo_frame_neighbours_kernel(

@@ -410,7 +410,7 @@ lod_emu_inter_build(
 }
 
 // ---- reflectance lifting with neighbours in a reference frame -----------------------------
-// The arrangement host_lift / launch_lift (gpcc_attr_mi355.hip) use for attribute inter
+// The arrangement host_lod_coder / launch_lift (gpcc_attr_mi355.hip) use for attribute inter
 // prediction: the frame's attributes in fixed point BEHIND the n working values, flagged
 // neighbours pointed there, the intra kernels unchanged.  One QP layer, one component.
 extern "C" int
@@ -494,7 +494,7 @@ lift_emu_inter(
 }
 
 // ---- the reflectance predicting transform with neighbours in a reference frame ---------------
-// pred_dag_kernel<1, ENC, true> with the arrangement host_pred / launch_pred use: flagged
+// pred_dag_kernel<1, ENC, true> with the arrangement host_lod_coder / launch_pred use: flagged
 // neighbours point behind the n predictors (PredCtx::frame_attr), the share arrays have spare
 // entries there.  Decoder and encoder, the latter's iteration over the rate model included.  One
 // QP layer.  The persistent kernels run as ONE workgroup here.

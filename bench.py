@@ -10,7 +10,13 @@ flags of cfg/octree-raht-ctc-lossless-geom-lossy-attrs.yaml (qp 34, search
 range 2500) and the reference's defaults for everything else, i.e.
 raht_subnode_prediction_enabled_flag = 1 (TMC3.cpp:1307).
 
-Extra objects of the same JSON line (rank 0, N=1):
+A plain run does what that figure needs and nothing else: it sets up, warms
+up, times the steps, writes --dump-outputs and prints the line.  Everything
+below that is measured or checked beside the headline -- the extra objects,
+the N>1 legs and verifications, the CPU comparison of --direction inverse --
+runs with --full only (about a minute more on one GPU).
+
+Extra objects of the same JSON line with --full (rank 0, N=1):
   roofline          dominant kernel of the headline step, priced with the
                     algorithmic bytes of ITS direction (SURVEY.md 8(d):
                     forward 8+12C, inverse 8+8C bytes per point)
@@ -25,11 +31,11 @@ Extra objects of the same JSON line (rank 0, N=1):
 
 With N>1 every rank transforms its own frame(s) (weak scaling: per-GPU work
 is fixed, frames shard one-per-GPU) and the quantised coefficients are
-gathered on rank 0 with one RCCL gather inside the timed region; the line
-then also carries `configs3`, the same measurement on BASELINE configs[3]'s
-2M-point dense frames.  What scales is transform + gather: the arithmetic
-coder that consumes the coefficients is the reference's CPU code and is not
-in the loop.
+gathered on rank 0 with one RCCL gather inside the timed region; with --full
+the line then also carries `configs3`, the same measurement on BASELINE
+configs[3]'s 2M-point dense frames.  What scales is transform + gather: the
+arithmetic coder that consumes the coefficients is the reference's CPU code
+and is not in the loop.
 
 Prints ONE JSON line (see the driver contract).  value = points entering
 the forward+inverse pass per second, whole job.
@@ -70,6 +76,10 @@ def parse():
                     help="inverse: decoder only (coefficients prepared on the CPU outside the timed region)")
     ap.add_argument("--configs3-points", type=int, default=2_000_000,
                     help="points per frame of the N>1 configs[3] leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures and checks: roofline, extra "
+                         "legs, CPU baselines and comparisons, the N>1 legs and verifications.  The options below that "
+                         "take parts of that away, or name legs, act with --full only")
     ap.add_argument("--verify-gather", dest="verify_gather", action="store_true", default=True,
                     help="N>1 (default): rank 0 recomputes every rank's frames itself and compares with what it gathered")
     ap.add_argument("--no-verify-gather", dest="verify_gather", action="store_false")
@@ -86,7 +96,14 @@ def parse():
                     help="skip the alternative-flag, 10M-forward, calibration and lifting legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step of the headline as DIR/<name>.npy")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        if args.legs:
+            ap.error("--legs names extra legs, and those run with --full only")
+        # a plain run: the headline alone
+        args.no_extras = args.no_profile = args.no_cpu_baseline = True
+        args.verify_gather = False
+    return args
 
 
 def make_frame(cloud, points, seed, refl_noise=6):
@@ -280,7 +297,7 @@ def main():
         # ... and ONE untimed comparison of that encoder with the CPU (the compiled reference where it is built,
         # else the oracle): a defect shared by the device encoder and decoder would otherwise still report
         # roundtrip_ok
-        if rank == 0:
+        if rank == 0 and args.full:
             try:
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 import oracle_loader as ol
@@ -374,7 +391,7 @@ def main():
         out["config"]["scaling_scope"] = ("transform + one RCCL gather of the coefficient buffers; the CPU "
                                           "arithmetic coder that consumes them is not in the loop")
 
-    if world > 1:
+    if world > 1 and args.full:
         # where a step's time goes on every rank: the transforms alone (device time, no collective) and the
         # gather alone, 3 steps each, every rank's figure on rank 0
         def rank_times(batch):

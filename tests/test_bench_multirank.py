@@ -21,14 +21,14 @@ def free_port():
         return s.getsockname()[1]
 
 
-def run_bench(world, points, c3, c4):
+def run_bench(world, points, c3, c4, full=True):
     env = dict(os.environ, GPCC_BENCH_BACKEND="gloo")
-    # (--verify-gather is the default for N > 1 since round 5)
+    # (with --full, --verify-gather is the default for N > 1 since round 5)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
            "--points", str(points), "--configs3-points", str(c3), "--configs4-points", str(c4),
-           "--frames-per-gpu-batched", "3"]
+           "--frames-per-gpu-batched", "3"] + (["--full"] if full else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -76,3 +76,14 @@ def test_bench_two_ranks_one_json_line():
     assert d["configs3"]["roundtrip_decoder_equals_encoder_recon"] is True and d["configs3"]["value"] > 0
     assert d["weak_batched"]["frames_per_gpu"] == 3 and len(d["weak_batched"]["device_ms_per_rank"]) == 2
     assert len(d["distributed"]["gather_ms_per_rank"]) == 2
+
+
+@pytest.mark.gpu
+def test_bench_two_ranks_plain_run_is_the_headline_alone():
+    """without --full: the timed steps with their gather and the line, none of the legs and verifications beside them"""
+    d = run_bench(2, 60000, 50000, 40000, full=False)
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["config"]["roundtrip_decoder_equals_encoder_recon"] is True
+    assert d["distributed"]["world_size"] == 2 and "device_ms_per_rank" not in d["distributed"]
+    assert "gathered_equals_single_rank" not in d["config"]
+    assert not {"weak_batched", "configs3", "configs4", "roofline", "cpu_baseline"} & set(d)

@@ -11,9 +11,9 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   echo "pytest rc $?" >> $OUT/pytest.log
   tail -4 $OUT/pytest.log
 fi
-( time timeout 600 python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+( time timeout 600 python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 300 $OUT/bench_default.err
-GPCC_PROFILE_LEVELS=1 timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 10 > $OUT/bench_levels.json 2> $OUT/bench_levels.err
+GPCC_PROFILE_LEVELS=1 timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 10 > $OUT/bench_levels.json 2> $OUT/bench_levels.err
 B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-profile"
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/kt -o kt -- bash -c "cd $GRAFT_REPO_ROOT && $B" > $GRAFT_REPO_ROOT/$OUT/kt.log 2>&1 )
 ( cd /tmp && timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_LDS -d $GRAFT_REPO_ROOT/$OUT/pmc_sq -o sq -- bash -c "cd $GRAFT_REPO_ROOT && $B" > $GRAFT_REPO_ROOT/$OUT/pmc_sq.log 2>&1 )

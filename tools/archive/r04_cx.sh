@@ -8,7 +8,7 @@ O=gpurun_out/${1:-r04_cx}; mkdir -p $O
 ( time timeout 900 python -m pytest tests/test_gpu_arith.py tests/test_gpu_raht.py tests/test_gpu_tile.py tests/test_gpu_batches.py -m gpu -x -q ) > $O/pytest.log 2>&1; tail -n 5 $O/pytest.log
 for f in 1 0; do
 for dir in forward inverse; do
-  GPCC_F64=$f timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 2 --subnode 0 --frames 10 --direction $dir > $O/bench_f64_${f}_$dir.json 2> $O/bench_f64_${f}_$dir.err
+  GPCC_F64=$f timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 10 --warmup 2 --subnode 0 --frames 10 --direction $dir > $O/bench_f64_${f}_$dir.json 2> $O/bench_f64_${f}_$dir.err
   python - <<PY
 import json
 try:

@@ -11,7 +11,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   echo "pytest rc $?" >> $OUT/pytest.log
   tail -5 $OUT/pytest.log
 fi
-( time timeout 900 python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+( time timeout 900 python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 200 $OUT/bench_default.err
 B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-profile"
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/kt -o kt -- bash -c "cd $GRAFT_REPO_ROOT && $B" > $GRAFT_REPO_ROOT/$OUT/kt.log 2>&1 )

@@ -9,7 +9,7 @@ O=gpurun_out/${1:-r04_rc}; mkdir -p $O
 timeout 600 python tools/recolour_time.py > $O/recolour_time.txt 2>&1; tail -n 4 $O/recolour_time.txt
 for cfg in "pipe:GPCC_PIPE=1" "lvl:GPCC_PIPE=0"; do
   name=${cfg%%:*}; envs=$(echo ${cfg#*:} | tr ',' ' ')
-  env $envs timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 20 > $O/bench_$name.json 2> $O/bench_$name.err
+  env $envs timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 20 > $O/bench_$name.json 2> $O/bench_$name.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${1:-r04_rdoq}; mkdir -p $O
 ( time timeout 1200 python -m pytest tests/test_gpu_raht.py tests/test_gpu_batches.py tests/test_gpu_arith.py tests/test_gpu_pipe.py -m gpu -x -q ) > $O/pytest.log 2>&1; tail -n 6 $O/pytest.log
 for q in 34 28 22 16 10; do
-  timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 10 --qp $q > $O/bench_qp$q.json 2> $O/bench_qp$q.err
+  timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 10 --qp $q > $O/bench_qp$q.json 2> $O/bench_qp$q.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=gpurun_out/r05_kt_pred
 mkdir -p $OUT
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/kt -o kt -- bash -c "cd $R && python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-profile --legs predicting" > $R/$OUT/kt.log 2>&1 )
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/kt -o kt -- bash -c "cd $R && python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-profile --legs predicting" > $R/$OUT/kt.log 2>&1 )
 find $OUT/kt -name '*kernel_stats*.csv' -exec cp {} $OUT/kernel_stats_pred.csv \;
 rm -rf $OUT/kt
 python - <<PY

@@ -16,7 +16,7 @@ for w in $WL; do
     headline)   B="python bench.py $COMMON" ;;
     fwd10_sub0) B="python bench.py $COMMON --frames 10 --direction forward --subnode 0" ;;
     fwd10_sub1) B="python bench.py $COMMON --frames 10 --direction forward --subnode 1" ;;
-    legs)       B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-profile --legs lifting,predicting,recolour,raht_inter" ;;
+    legs)       B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-profile --legs lifting,predicting,recolour,raht_inter" ;;
   esac
   R=$GRAFT_REPO_ROOT
   ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/kt_$w -o kt -- bash -c "cd $R && $B" > $R/$OUT/kt_$w.log 2>&1 )

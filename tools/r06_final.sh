@@ -9,6 +9,6 @@ mkdir -p $OUT
 echo "pytest rc $?" >> $OUT/pytest.log
 tail -n 6 $OUT/pytest.log
 ( time timeout 300 python -c "import __graft_entry__ as g; g.smoke()" ) > $OUT/smoke.log 2>&1; tail -n 3 $OUT/smoke.log
-( time timeout 900 python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+( time timeout 900 python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 400 $OUT/bench_default.err
 head -c 600 $OUT/bench_default.json

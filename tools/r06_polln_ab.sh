@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out/r06_polln
 for v in base pn2 pn3 pn4 base pn2; do
   if [ $v = base ]; then L=""; else L="GPCC_LIB_PATH=exp/libgpcc_$v.so"; fi
-  env $L timeout 300 python bench.py --no-extras --steps 20 --no-cpu-baseline 2>/dev/null | python -c "
+  env $L timeout 300 python bench.py --full --no-extras --steps 20 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().splitlines()[-1]); r=d['roofline']
 print('$v', d['value'], 'Mpts/s', d['ms_per_step'], 'ms; fwd', r['forward_kernel_ms'].get('level_sub_lossy'), 'inv', r['inverse_kernel_ms'].get('level_sub_synth'), 'roundtrip', d['config']['roundtrip_decoder_equals_encoder_recon'])" | tee -a gpurun_out/r06_polln/ab.txt

@@ -3,7 +3,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"
 N=${1:-r06_sweep}
-bash tools/r06_gpu.sh $N "tests/test_gpu_raht.py tests/test_gpu_batches.py tests/test_gpu_regions.py tests/test_gpu_tile.py" "on|GPCC_SWEEP=1|--no-extras --steps 10 --no-cpu-baseline" "on22|GPCC_SWEEP=1|--no-extras --steps 10 --no-cpu-baseline --qp 22" > gpurun_out/${N}_stdout.txt 2>&1
+bash tools/r06_gpu.sh $N "tests/test_gpu_raht.py tests/test_gpu_batches.py tests/test_gpu_regions.py tests/test_gpu_tile.py" "on|GPCC_SWEEP=1|--full --no-extras --steps 10 --no-cpu-baseline" "on22|GPCC_SWEEP=1|--full --no-extras --steps 10 --no-cpu-baseline --qp 22" 2>&1
 GPCC_LIB_PATH=exp/libgpcc_subprof.so python tools/sweep_prof.py 1 forward > gpurun_out/$N/prof_fwd.txt 2>&1
 GPCC_LIB_PATH=exp/libgpcc_subprof.so python tools/sweep_prof.py 1 inverse > gpurun_out/$N/prof_inv.txt 2>&1
 grep -E "passed|failed|FAILED" gpurun_out/$N/pytest.log

@@ -152,11 +152,21 @@ typedef struct gpcc_ctx_stats_t {
 int gpcc_ctx_stats(const gpcc_ctx* ctx, gpcc_ctx_stats_t* out);
 
 /* The predicting encoder with direct predictors iterates its reconstruction pass and the rate
- * model's trajectory to their fixed point (see gpcc_pred_forward); a slice that has not settled
- * within the pass limit (64) is declined.  out[0] slices coded that way since the context was
- * created, out[1] passes over all of them, out[2] the most passes one slice took, out[3] slices
- * declined at the limit (none observed so far: bench.py's predicting leg reports these). */
+ * model's trajectory towards their fixed point (see gpcc_pred_forward).  out[0] slices coded that
+ * way since the context was created, out[1] passes over all of them, out[2] the most passes one
+ * slice took, out[3] slices declined at the pass limit: always 0 -- a slice whose passes do not
+ * settle is finished by the ordered walk below, none is declined (bench.py's predicting leg
+ * reports these). */
 int gpcc_ctx_pred_pass_stats(const gpcc_ctx* ctx, int64_t out[4]);
+
+/* The finish of that encoder: a slice that has not settled after GPCC_PRED_REPAIR_AFTER passes
+ * (environment, read when the context is created; default 32, at most 64) is completed by a walk
+ * in coding order over the decisions the passes left open (see gpcc_pred_forward).  out[0] slices
+ * that entered the walk since the context was created, out[1] predictors walked, out[2] stretches
+ * walked (a stretch runs from a wrong decision to the predictor where the rate state agrees
+ * again), out[3] the longest stretch.  Summed over the lanes of the device tier as the pass
+ * statistics are. */
+int gpcc_ctx_pred_repair_stats(const gpcc_ctx* ctx, int64_t out[4]);
 
 /* ------------------------------------------------------------------ */
 /* host tier: one slice, host buffers, synchronous                      */
@@ -708,8 +718,14 @@ int gpcc_slice_rdo_choose(
  * states from the pass's values, and repeats until a pass changes no value --
  * the sequential coder's result (a few passes per slice).  The estimate's log2
  * values come from a table filled by the HOST's libm, so the doubles are the
- * reference's.  A slice that has not settled after 64 passes returns
- * GPCC_ERR_UNSUPPORTED with attrs restored (not observed). */
+ * reference's.  Noisy content at low QP leaves a handful of near-tie decisions
+ * that chase each other through the rate state from pass to pass: after
+ * GPCC_PRED_REPAIR_AFTER passes (default 32) one wavefront walks the predictors
+ * in coding order from the first decision that still differs, with the exact
+ * rate state, and skips whatever the last pass already has right -- exact and
+ * always finite, so no slice is declined for its content
+ * (gpcc_ctx_pred_repair_stats).  Every predicting encoder entry below shares
+ * this. */
 int gpcc_pred_forward(
   gpcc_ctx* ctx, const gpcc_pred_params* params, int32_t n, int32_t c,
   const int32_t* neigh_count, const int32_t* neigh_index,
@@ -864,8 +880,9 @@ int gpcc_dev_lift_decode_attr_partial(
  *   pred   [num_slices] parameter blocks (in: tools, QP; out: the LoD structure)
  *   d_attrs [N][c] point order; d_values [N][c] coding order per slice
  *   icp_coeffs host [num_slices][GPCC_MAX_LODS][3] (c == 3 and the flag set)
- *   d_indexes [N] out, may be NULL.  The encoder declines direct predictors
- *   (GPCC_ERR_UNSUPPORTED), see gpcc_pred_forward. */
+ *   d_indexes [N] out, may be NULL.  The encoder with direct predictors as
+ *   gpcc_pred_forward: passes, then the ordered walk where they do not settle
+ *   (every lane keeps its own statistics, gpcc_ctx_pred_repair_stats adds them up). */
 int gpcc_dev_pred_encode_attr(
   gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred,
   int32_t num_slices, const int64_t* offsets, const void* d_xyz, void* d_attrs,

@@ -47,6 +47,7 @@
 #include "lod_kernels.hpp"
 #include "lod_scalable.hpp"
 #include "pred_kernels.hpp"
+#include "pred_repair.hpp"
 #include "morton_sort.hpp"
 #include "residual_bins.hpp"
 #include "recolour_kernels.hpp"
@@ -291,7 +292,11 @@ struct gpcc_ctx {
   void* sweep_mem = nullptr;      // records of the coarse-level sweep (raht_sweep.hpp), grown on demand
   size_t sweep_cap = 0;
   int pred_passes = 0;            // passes the last predicting encode with direct predictors took
-  int64_t pred_pass_stats[4] = {0, 0, 0, 0};  // slices, passes, most passes, declined at the limit
+  int64_t pred_pass_stats[4] = {0, 0, 0, 0};  // slices, passes, most passes, declined at the limit (stays 0)
+  // the encoder's finish (pred_repair.hpp): slices that entered it, predictors walked, stretches walked, longest stretch
+  int64_t pred_repair_stats[4] = {0, 0, 0, 0};
+  // whole-slice passes before the walk takes over (GPCC_PRED_REPAIR_AFTER, read once per context)
+  int pred_repair_after = pred_repair_after_from_text(getenv("GPCC_PRED_REPAIR_AFTER"));
   hipEvent_t ev_stats = nullptr;  // recorded behind schedule_kernel
   // recolour: the second tree's build runs on a stream of its own (recolour_kdtree.hpp KdLevelLoop)
   hipStream_t kd_stream = nullptr;
@@ -1999,18 +2004,6 @@ rc_scan(gpcc_ctx* ctx, int32_t* a, size_t n, long long* sums)
   return GPCC_OK;
 }
 
-// the predicting encoder's mode decisions did not settle (see pred_kernels.hpp)
-int
-pred_encoder_unsettled()
-{
-  return fail(
-    GPCC_ERR_UNSUPPORTED,
-    "the encoder's choice among direct predictors did not settle within the pass limit: "
-    "this slice stays on the reference CPU path");
-}
-
-constexpr int kPredMaxPasses = 64;
-
 int
 check_pred_params(const gpcc_pred_params* p, int n, int c, bool encoder)
 {
@@ -2050,7 +2043,9 @@ pred_scratch_bytes(int n, int n_frame = 0)
   ar.take<int32_t>(64);
   ar.take<unsigned long long>(GPCC_MAX_LODS * 18);
   // encoder with direct predictors: rate model per predictor, source copy, previous values,
-  // ranks / events / event states of the probResGt1 recurrence, scan sums
+  // ranks / events / event states of the probResGt1 recurrence, scan sums (the finish of
+  // pred_repair.hpp takes its difference ranks, marks and list from the same three arrays: the
+  // recurrence does not run while it does)
   ar.take<int32_t>((size_t)n * 6);
   ar.take<int32_t>((size_t)n * 3);
   ar.take<int32_t>((size_t)n * 3);
@@ -2086,39 +2081,7 @@ launch_pred(
   cx.num_lods = p->num_lods;
   for (int l = 0; l < p->num_lods; l++)
     cx.npl[l] = p->num_points_in_lod[l];
-  // The reference's running counters step when the predictor index meets
-  // numPointsInLod[counter] (one step per index, so a repeated boundary
-  // stalls them): quantLayer and `lod` of the coding loops
-  // (AttributeEncoder.cpp:1108-1121, AttributeDecoder.cpp:476-501) before the
-  // index is processed, `lod` of computeInterComponentPredictionCoeffs
-  // (:1033-1056) after index npl[lod] - 1.  Replayed over the distinct
-  // boundaries.
-  {
-    int ql = 0, lod = 0, est = 0, nr = 1;
-    std::vector<int> bs(p->num_points_in_lod, p->num_points_in_lod + p->num_lods);
-    std::sort(bs.begin(), bs.end());
-    bs.erase(std::unique(bs.begin(), bs.end()), bs.end());
-    cx.range_start[0] = 0;
-    for (int b : bs) {
-      if (b >= n)
-        break;
-      if (ql < p->num_lods && b == p->num_points_in_lod[ql])
-        ql = std::min(p->num_qp_layers - 1, ql + 1);
-      if (lod < p->num_lods && b == p->num_points_in_lod[lod])
-        lod++;
-      if (b > 0 && est < p->num_lods && b == p->num_points_in_lod[est])
-        est++;
-      if (b > 0) {
-        cx.range_start[nr] = b;
-        nr++;
-      }
-      cx.range_qlayer[nr - 1] = ql;
-      cx.range_lod[nr - 1] = std::min(lod, GPCC_MAX_LODS - 1);
-      cx.range_est[nr - 1] = std::min(est, GPCC_MAX_LODS - 1);
-    }
-    cx.num_ranges = nr;
-    cx.est_resolved = est < p->num_lods && p->num_points_in_lod[est] == n ? est + 1 : est;
-  }
+  pred_fill_ranges(cx, p->num_points_in_lod, p->num_lods, p->num_qp_layers, n);
   cx.max_levels = p->max_num_detail_levels;
   cx.bitdepth = p->bitdepth;
   cx.num_qp_layers = p->num_qp_layers;
@@ -2229,8 +2192,9 @@ launch_pred(
       pred_rate_init_kernel<<<grid(n), 256, 0, st>>>(rm, n);
     }
     bool settled = false;
-    int passes = 0;
-    for (int pass = 0; pass < kPredMaxPasses && !settled; pass++) {
+    int passes = 0, differences = 0;
+    const int after = ctx->pred_repair_after;
+    for (int pass = 0; !settled && !differences; pass++) {
       passes++;
       cx.tag = (uint32_t)(pass + 1);
       HIP_TRY(hipMemsetAsync(cx.ticket, 0, 8 * sizeof(int32_t), st));
@@ -2238,6 +2202,20 @@ launch_pred(
       {
         Timer t(ctx, "pred_dag");
         GPCC_PRED_DAG(true);
+      }
+      if (pred_repair_pass_lists(pass, after)) {
+        // the last whole-slice pass: its differences as an ordered list (ranks, then the list), for the walk
+        Timer t(ctx, "pred_repair");
+        pred_diff_flags_kernel<<<grid(n), 256, 0, st>>>(cx.values, pass > 0 ? prev_values : nullptr, n, C, ev_rank);
+        int r = rc_scan(ctx, ev_rank, (size_t)n + 1, scan_sums);
+        if (r)
+          return r;
+        int32_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, ev_rank + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        differences = total;
+        settled = total == 0;
+        break;
       }
       int32_t changed = 1;
       {
@@ -2270,12 +2248,31 @@ launch_pred(
     ctx->pred_pass_stats[0]++;
     ctx->pred_pass_stats[1] += passes;
     ctx->pred_pass_stats[2] = std::max<int64_t>(ctx->pred_pass_stats[2], passes);
-    ctx->pred_pass_stats[3] += settled ? 0 : 1;
     if (!settled) {
-      // the caller's attrs hold a reconstruction that is not the reference's: restore the source
-      HIP_TRY(hipMemcpyAsync(d.attrs, src_copy, sizeof(int32_t) * (size_t)n * C, hipMemcpyDeviceToDevice, st));
+      // the finish (pred_kernels.hpp, "the encoder's finish"): one wavefront walks, in coding order and with the
+      // exact state, what the passes left undecided; it ends at n with the sequential coder's result
+      Timer t(ctx, "pred_repair");
+      PredWalk w{};
+      w.rank = ev_rank;
+      w.list = ev_state;
+      w.changed = ev_up;
+      w.out = small + 32;
+      HIP_TRY(hipMemsetAsync(ev_up, 0, (size_t)n, st));
+      HIP_TRY(hipMemsetAsync(w.out, 0, 4 * sizeof(int32_t), st));
+      pred_diff_list_kernel<<<grid(n), 256, 0, st>>>(ev_rank, n, ev_state);
+      if (n_frame > 0)
+        pred_walk_kernel<C, true><<<1, 64, 0, st>>>(cx, w);
+      else
+        pred_walk_kernel<C, false><<<1, 64, 0, st>>>(cx, w);
+      int32_t out[4] = {0, 0, 0, 0};
+      HIP_TRY(hipMemcpyAsync(out, w.out, sizeof(out), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
-      return pred_encoder_unsettled();
+      if (!pred_repair_walk_complete(out, n, differences))
+        return fail(GPCC_ERR_HIP, "the predicting encoder's ordered walk did not reach the end of the slice");
+      ctx->pred_repair_stats[0]++;
+      ctx->pred_repair_stats[1] += out[0];
+      ctx->pred_repair_stats[2] += out[1];
+      ctx->pred_repair_stats[3] = std::max<int64_t>(ctx->pred_repair_stats[3], out[2]);
     }
   }
 #undef GPCC_PRED_DAG
@@ -2794,6 +2791,21 @@ gpcc_ctx_pred_pass_stats(const gpcc_ctx* ctx, int64_t out[4])
     out[1] += lane->pred_pass_stats[1];
     out[2] = std::max(out[2], lane->pred_pass_stats[2]);
     out[3] += lane->pred_pass_stats[3];
+  }
+  return GPCC_OK;
+}
+
+extern "C" int
+gpcc_ctx_pred_repair_stats(const gpcc_ctx* ctx, int64_t out[4])
+{
+  if (!ctx || !out)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx or out is null");
+  for (int k = 0; k < 4; k++)
+    out[k] = ctx->pred_repair_stats[k];
+  for (const gpcc_ctx* lane : ctx->lanes) {
+    for (int k = 0; k < 3; k++)
+      out[k] += lane->pred_repair_stats[k];
+    out[3] = std::max(out[3], lane->pred_repair_stats[3]);
   }
   return GPCC_OK;
 }
@@ -3878,7 +3890,7 @@ code_slice(
     return r;
   r = Coder::launch(ctx, encoder, p, n, c, d, b.side, b.scratch, n_frame, frame, partial);
   if (r)
-    return r;  // (a predicting encoder that did not settle: pred_encoder_unsettled)
+    return r;
   r = collect(b);
   if (r)
     return r;

@@ -28,6 +28,9 @@
 // (the caller keeps the reference's loop).
 #pragma once
 
+#include <algorithm>
+#include <vector>
+
 #include "lift_kernels.hpp"
 
 namespace gpcc {
@@ -89,6 +92,42 @@ struct PredCtx {
   // (computeQuantizationWeights :913-914) land there.
   const int32_t* frame_attr;  // [n_frame]
 };
+
+// The reference's running counters step when the predictor index meets
+// numPointsInLod[counter] (one step per index, so a repeated boundary
+// stalls them): quantLayer and `lod` of the coding loops
+// (AttributeEncoder.cpp:1108-1121, AttributeDecoder.cpp:476-501) before the
+// index is processed, `lod` of computeInterComponentPredictionCoeffs
+// (:1033-1056) after index npl[lod] - 1.  Replayed over the distinct
+// boundaries.
+inline void
+pred_fill_ranges(PredCtx& cx, const int32_t* npl, int num_lods, int num_qp_layers, int n)
+{
+  int ql = 0, lod = 0, est = 0, nr = 1;
+  std::vector<int> bs(npl, npl + num_lods);
+  std::sort(bs.begin(), bs.end());
+  bs.erase(std::unique(bs.begin(), bs.end()), bs.end());
+  cx.range_start[0] = 0;
+  for (int b : bs) {
+    if (b >= n)
+      break;
+    if (ql < num_lods && b == npl[ql])
+      ql = std::min(num_qp_layers - 1, ql + 1);
+    if (lod < num_lods && b == npl[lod])
+      lod++;
+    if (b > 0 && est < num_lods && b == npl[est])
+      est++;
+    if (b > 0) {
+      cx.range_start[nr] = b;
+      nr++;
+    }
+    cx.range_qlayer[nr - 1] = ql;
+    cx.range_lod[nr - 1] = std::min(lod, GPCC_MAX_LODS - 1);
+    cx.range_est[nr - 1] = std::min(est, GPCC_MAX_LODS - 1);
+  }
+  cx.num_ranges = nr;
+  cx.est_resolved = est < num_lods && npl[est] == n ? est + 1 : est;
+}
 
 __device__ __forceinline__ int
 pred_range_of(const PredCtx& cx, int i)
@@ -625,6 +664,218 @@ pred_values_diff_kernel(const int32_t* __restrict__ values, int32_t* __restrict_
     atomicOr(flag, 1);
 }
 
+// One predictor, from its neighbours' reconstructions to its coded values and its own
+// reconstruction: eligibility for direct prediction, the mode (decoder: unfolded from the value
+// parities; encoder: decided with the rate model `rm` -- the six words in front of THIS predictor),
+// prediction, residual, reconstruction and, in the encoder, the mode folded into the values.
+// The one statement of the per-predictor step: pred_dag_kernel runs it for a lane of a claim,
+// pred_walk_kernel for the predictor its walk stands at.
+template<int C, bool ENC>
+__device__ __forceinline__ void
+pred_point(
+  const PredCtx& cx, const int32_t* rm, int cnt, const int32_t (&nbv)[3][C], const int32_t (&nwt)[3],
+  const int32_t (&col)[3], const Quantizer (&q)[2], const int64_t (&wgt)[2], const int8_t (&icpc)[3], int maxcand,
+  int64_t clip_max, int32_t (&val)[3], int32_t (&myrec)[C])
+{
+  // predModeEligibleColor / ...Refl
+  bool elig = false;
+  if (cnt > 1 && cx.max_direct) {
+    int32_t best = 0;
+    for (int k = 0; k < C; k++) {
+      int32_t lo = nbv[0][k], hi = nbv[0][k];
+      for (int j = 1; j < 3; j++)
+        if (j < cnt) {
+          lo = min(lo, nbv[j][k]);
+          hi = max(hi, nbv[j][k]);
+        }
+      best = k == 0 ? hi - lo : max(best, hi - lo);
+    }
+    elig = best >= cx.threshold;
+  }
+  int mode = 0;
+  if (!ENC && elig) {
+    if (C == 1) {
+      // decodePredModeRefl
+      int a = abs(val[0]);
+      const int sg = val[0] < 0 ? -1 : 1;
+      if (maxcand == 4) {
+        mode = a & 3;
+        a >>= 2;
+      } else if (maxcand == 3) {
+        mode = a & 1;
+        a >>= 1;
+        if (mode > 0) {
+          mode += a & 1;
+          a >>= 1;
+        }
+      } else if (maxcand == 2) {
+        mode = a & 1;
+        a >>= 1;
+      }
+      val[0] = sg * a;
+    } else {
+      // decodePredModeColor
+      const int s1 = val[1 % C] < 0 ? -1 : 1, s2 = val[2 % C] < 0 ? -1 : 1;
+      const int a1 = abs(val[1 % C]), a2 = abs(val[2 % C]);
+      if (maxcand == 4) {
+        val[1 % C] = s1 * (a1 >> 1);
+        val[2 % C] = s2 * (a2 >> 1);
+        mode = ((a1 & 1) << 1) + (a2 & 1);
+      } else if (maxcand == 3) {
+        val[1 % C] = s1 * (a1 >> 1);
+        mode = a1 & 1;
+        if (a1 & 1) {
+          val[2 % C] = s2 * (a2 >> 1);
+          mode += a2 & 1;
+        }
+      } else if (maxcand == 2) {
+        val[1 % C] = s1 * (a1 >> 1);
+        mode = a1 & 1;
+      }
+    }
+    mode += cx.avg_disabled;
+  }
+  if (ENC && elig) {
+    // decidePredModeRefl / decidePredModeColor with the rate model as it is
+    // before this predictor
+#pragma clang fp contract(off)
+    const int dis = cx.avg_disabled;
+    mode = dis;
+    int64_t p0[3] = {0, 0, 0};
+    if (dis) {
+      for (int k = 0; k < C; k++)
+        p0[k] = nbv[0][k];
+    } else {
+      for (int k = 0; k < C; k++) {
+        int64_t s = 0;
+        for (int j = 0; j < 3; j++)
+          if (j < cnt)
+            s += (int64_t)(uint32_t)nwt[j] * nbv[j][k];
+        p0[k] = (uint16_t)div_exp2_round_half_inf(s, 8);
+      }
+    }
+    if (C == 1) {
+      int64_t rq = quantize(q[0], ((int64_t)col[0] - p0[0]) << 8);
+      int64_t best = (int64_t)pred_rate_refl(cx, rm, maxcand, (int32_t)rq, mode - dis);
+      for (int j = 0; j < 3; j++) {
+        if (j < dis || j >= cnt || j >= cx.max_direct)
+          continue;
+        rq = quantize(q[0], ((int64_t)col[0] - (int64_t)nbv[j][0]) << 8);
+        const int64_t score = (int64_t)pred_rate_refl(cx, rm, maxcand, (int32_t)rq, j + !dis);
+        if (score < best) {
+          best = score;
+          mode = j + 1;
+        }
+      }
+    } else {
+      int32_t c3[3] = {col[0], col[1 % C], col[2 % C]};
+      int64_t r[3];
+      pred_colour_residuals(cx.icp_enabled != 0, c3, p0, icpc, q, r);
+      int dist = pred_colour_distortion(clip_max, c3, p0, q);
+      double rate = pred_rate_colour(cx, rm, maxcand, r, 0);
+      double best = dist + rate * 0.14 * (q[0].step >> 8);
+      for (int j = 0; j < 3; j++) {
+        if (j < dis || j >= cnt || j >= cx.max_direct)
+          continue;
+        const int64_t np[3] = {nbv[j][0], nbv[j][1 % C], nbv[j][2 % C]};
+        pred_colour_residuals(cx.icp_enabled != 0, c3, np, icpc, q, r);
+        dist = pred_colour_distortion(clip_max, c3, np, q);
+        rate = pred_rate_colour(cx, rm, maxcand, r, j + !dis);
+        const double score = dist + rate * 0.14 * (q[0].step >> 8);
+        if (score < best) {
+          best = score;
+          mode = j + 1;
+        }
+      }
+    }
+  }
+  // PCCPredictor::predictColor / predictReflectance
+  int64_t pr[C];
+  for (int k = 0; k < C; k++)
+    pr[k] = 0;
+  if (mode > cnt) {
+  } else if (mode > 0) {
+    // (the three values first, the choice among VALUES: a choice among the loads becomes one load at a
+    // computed address, and the neighbour block then lives in scratch)
+    for (int k = 0; k < C; k++) {
+      const int32_t v0 = nbv[0][k], v1 = nbv[1][k], v2 = nbv[2][k];
+      pr[k] = mode == 1 ? v0 : (mode == 2 ? v1 : v2);
+    }
+  } else {
+    for (int k = 0; k < C; k++) {
+      int64_t s = 0;
+      for (int j = 0; j < 3; j++)
+        if (j < cnt)
+          s += (int64_t)(uint32_t)nwt[j] * nbv[j][k];
+      pr[k] = (uint16_t)div_exp2_round_half_inf(s, 8);
+    }
+  }
+  int64_t residual0 = 0;
+  for (int k = 0; k < C; k++) {
+    const Quantizer qq = k ? q[1] : q[0];
+    const int64_t weight = k ? wgt[1] : wgt[0];
+    const int64_t icpterm = C == 3 ? ((int64_t)icpc[k] * residual0 + 2) >> 2 : 0;
+    int64_t rr;
+    if (ENC) {
+      int64_t residual = col[k] - pr[k];
+      int64_t rq = quantize(qq, (residual * weight) << 8);
+      rr = ((mul_i64_u32(rq, qq.step) + 128) >> 8) / weight;
+      if (C == 3 && cx.icp_enabled && k > 0) {
+        residual -= icpterm;
+        rq = quantize(qq, (residual * weight) << 8);
+        rr = ((mul_i64_u32(rq, qq.step) + 128) >> 8) / weight;
+        rr += icpterm;
+      }
+      val[k] = (int32_t)rq;
+      if (k == 0)
+        residual0 = rr;
+    } else {
+      rr = ((mul_i64_u32((int64_t)val[k], qq.step) + 128) >> 8) / weight;
+      const int64_t residual = rr;
+      rr += icpterm;
+      if (!k && cx.icp_enabled)
+        residual0 = residual;
+    }
+    int64_t v = pr[k] + rr;
+    v = v < 0 ? 0 : (v > clip_max ? clip_max : v);
+    myrec[k] = (int32_t)(uint16_t)v;
+  }
+  if (ENC && elig) {
+    // encodePredModeRefl (:749-772) / encodePredModeColor (:988-1016): the mode
+    // travels in the low bits of the coded magnitudes
+    const int m = mode - cx.avg_disabled;
+    if (C == 1) {
+      const int sg = val[0] < 0 ? -1 : 1;
+      int a = val[0] < 0 ? -val[0] : val[0];
+      if (maxcand == 4) {
+        a = (a << 2) + m;
+      } else if (maxcand == 3) {
+        if (m > 0)
+          a = (a << 1) + (m - 1);
+        a = (a << 1) + (m > 0);
+      } else if (maxcand == 2) {
+        a = (a << 1) + m;
+      }
+      val[0] = sg * a;
+    } else {
+      const int s1 = val[1 % C] < 0 ? -1 : 1, s2 = val[2 % C] < 0 ? -1 : 1;
+      const int a1 = val[1 % C] < 0 ? -val[1 % C] : val[1 % C];
+      const int a2 = val[2 % C] < 0 ? -val[2 % C] : val[2 % C];
+      if (maxcand == 4) {
+        val[1 % C] = s1 * ((a1 << 1) + (m >> 1));
+        val[2 % C] = s2 * ((a2 << 1) + (m & 1));
+      } else if (maxcand == 3) {
+        const int p1 = m ? 1 : 0;
+        val[1 % C] = s1 * ((a1 << 1) + p1);
+        if (p1)
+          val[2 % C] = s2 * ((a2 << 1) + (m - p1));
+      } else if (maxcand == 2) {
+        val[1 % C] = s1 * ((a1 << 1) + m);
+      }
+    }
+  }
+}
+
 // ---- reconstruction: the DAG walked forward --------------------------------
 template<int C, bool ENC, bool INTER = false>
 __global__ __launch_bounds__(256) void
@@ -742,200 +993,8 @@ pred_dag_kernel(PredCtx cx)
       }
       const bool ready = pending && have == want;
       if (ready) {
-        // predModeEligibleColor / ...Refl
-        bool elig = false;
-        if (cnt > 1 && cx.max_direct) {
-          int32_t best = 0;
-          for (int k = 0; k < C; k++) {
-            int32_t lo = nbv[0][k], hi = nbv[0][k];
-            for (int j = 1; j < 3; j++)
-              if (j < cnt) {
-                lo = min(lo, nbv[j][k]);
-                hi = max(hi, nbv[j][k]);
-              }
-            best = k == 0 ? hi - lo : max(best, hi - lo);
-          }
-          elig = best >= cx.threshold;
-        }
-        int mode = 0;
-        if (!ENC && elig) {
-          if (C == 1) {
-            // decodePredModeRefl
-            int a = abs(val[0]);
-            const int sg = val[0] < 0 ? -1 : 1;
-            if (maxcand == 4) {
-              mode = a & 3;
-              a >>= 2;
-            } else if (maxcand == 3) {
-              mode = a & 1;
-              a >>= 1;
-              if (mode > 0) {
-                mode += a & 1;
-                a >>= 1;
-              }
-            } else if (maxcand == 2) {
-              mode = a & 1;
-              a >>= 1;
-            }
-            val[0] = sg * a;
-          } else {
-            // decodePredModeColor
-            const int s1 = val[1 % C] < 0 ? -1 : 1, s2 = val[2 % C] < 0 ? -1 : 1;
-            const int a1 = abs(val[1 % C]), a2 = abs(val[2 % C]);
-            if (maxcand == 4) {
-              val[1 % C] = s1 * (a1 >> 1);
-              val[2 % C] = s2 * (a2 >> 1);
-              mode = ((a1 & 1) << 1) + (a2 & 1);
-            } else if (maxcand == 3) {
-              val[1 % C] = s1 * (a1 >> 1);
-              mode = a1 & 1;
-              if (a1 & 1) {
-                val[2 % C] = s2 * (a2 >> 1);
-                mode += a2 & 1;
-              }
-            } else if (maxcand == 2) {
-              val[1 % C] = s1 * (a1 >> 1);
-              mode = a1 & 1;
-            }
-          }
-          mode += cx.avg_disabled;
-        }
-        if (ENC && elig) {
-          // decidePredModeRefl / decidePredModeColor with the rate model as it is
-          // before this predictor
-#pragma clang fp contract(off)
-          const int32_t* rm = cx.rm + (size_t)i * 6;
-          const int dis = cx.avg_disabled;
-          mode = dis;
-          int64_t p0[3] = {0, 0, 0};
-          if (dis) {
-            for (int k = 0; k < C; k++)
-              p0[k] = nbv[0][k];
-          } else {
-            for (int k = 0; k < C; k++) {
-              int64_t s = 0;
-              for (int j = 0; j < 3; j++)
-                if (j < cnt)
-                  s += (int64_t)(uint32_t)nwt[j] * nbv[j][k];
-              p0[k] = (uint16_t)div_exp2_round_half_inf(s, 8);
-            }
-          }
-          if (C == 1) {
-            int64_t rq = quantize(q[0], ((int64_t)col[0] - p0[0]) << 8);
-            int64_t best = (int64_t)pred_rate_refl(cx, rm, maxcand, (int32_t)rq, mode - dis);
-            for (int j = 0; j < 3; j++) {
-              if (j < dis || j >= cnt || j >= cx.max_direct)
-                continue;
-              rq = quantize(q[0], ((int64_t)col[0] - (int64_t)nbv[j][0]) << 8);
-              const int64_t score = (int64_t)pred_rate_refl(cx, rm, maxcand, (int32_t)rq, j + !dis);
-              if (score < best) {
-                best = score;
-                mode = j + 1;
-              }
-            }
-          } else {
-            int32_t c3[3] = {col[0], col[1 % C], col[2 % C]};
-            int64_t r[3];
-            pred_colour_residuals(cx.icp_enabled != 0, c3, p0, icpc, q, r);
-            int dist = pred_colour_distortion(clip_max, c3, p0, q);
-            double rate = pred_rate_colour(cx, rm, maxcand, r, 0);
-            double best = dist + rate * 0.14 * (q[0].step >> 8);
-            for (int j = 0; j < 3; j++) {
-              if (j < dis || j >= cnt || j >= cx.max_direct)
-                continue;
-              const int64_t np[3] = {nbv[j][0], nbv[j][1 % C], nbv[j][2 % C]};
-              pred_colour_residuals(cx.icp_enabled != 0, c3, np, icpc, q, r);
-              dist = pred_colour_distortion(clip_max, c3, np, q);
-              rate = pred_rate_colour(cx, rm, maxcand, r, j + !dis);
-              const double score = dist + rate * 0.14 * (q[0].step >> 8);
-              if (score < best) {
-                best = score;
-                mode = j + 1;
-              }
-            }
-          }
-        }
-        // PCCPredictor::predictColor / predictReflectance
-        int64_t pr[C];
-        for (int k = 0; k < C; k++)
-          pr[k] = 0;
-        if (mode > cnt) {
-        } else if (mode > 0) {
-          for (int k = 0; k < C; k++)
-            pr[k] = mode == 1 ? nbv[0][k] : (mode == 2 ? nbv[1][k] : nbv[2][k]);
-        } else {
-          for (int k = 0; k < C; k++) {
-            int64_t s = 0;
-            for (int j = 0; j < 3; j++)
-              if (j < cnt)
-                s += (int64_t)(uint32_t)nwt[j] * nbv[j][k];
-            pr[k] = (uint16_t)div_exp2_round_half_inf(s, 8);
-          }
-        }
-        int64_t residual0 = 0;
-        for (int k = 0; k < C; k++) {
-          const Quantizer qq = q[k ? 1 : 0];
-          const int64_t weight = wgt[k ? 1 : 0];
-          const int64_t icpterm = C == 3 ? ((int64_t)icpc[k] * residual0 + 2) >> 2 : 0;
-          int64_t rr;
-          if (ENC) {
-            int64_t residual = col[k] - pr[k];
-            int64_t rq = quantize(qq, (residual * weight) << 8);
-            rr = ((mul_i64_u32(rq, qq.step) + 128) >> 8) / weight;
-            if (C == 3 && cx.icp_enabled && k > 0) {
-              residual -= icpterm;
-              rq = quantize(qq, (residual * weight) << 8);
-              rr = ((mul_i64_u32(rq, qq.step) + 128) >> 8) / weight;
-              rr += icpterm;
-            }
-            val[k] = (int32_t)rq;
-            if (k == 0)
-              residual0 = rr;
-          } else {
-            rr = ((mul_i64_u32((int64_t)val[k], qq.step) + 128) >> 8) / weight;
-            const int64_t residual = rr;
-            rr += icpterm;
-            if (!k && cx.icp_enabled)
-              residual0 = residual;
-          }
-          int64_t v = pr[k] + rr;
-          v = v < 0 ? 0 : (v > clip_max ? clip_max : v);
-          myrec[k] = (int32_t)(uint16_t)v;
-        }
-        if (ENC && elig) {
-          // encodePredModeRefl (:749-772) / encodePredModeColor (:988-1016): the mode
-          // travels in the low bits of the coded magnitudes
-          const int m = mode - cx.avg_disabled;
-          if (C == 1) {
-            const int sg = val[0] < 0 ? -1 : 1;
-            int a = val[0] < 0 ? -val[0] : val[0];
-            if (maxcand == 4) {
-              a = (a << 2) + m;
-            } else if (maxcand == 3) {
-              if (m > 0)
-                a = (a << 1) + (m - 1);
-              a = (a << 1) + (m > 0);
-            } else if (maxcand == 2) {
-              a = (a << 1) + m;
-            }
-            val[0] = sg * a;
-          } else {
-            const int s1 = val[1 % C] < 0 ? -1 : 1, s2 = val[2 % C] < 0 ? -1 : 1;
-            const int a1 = val[1 % C] < 0 ? -val[1 % C] : val[1 % C];
-            const int a2 = val[2 % C] < 0 ? -val[2 % C] : val[2 % C];
-            if (maxcand == 4) {
-              val[1 % C] = s1 * ((a1 << 1) + (m >> 1));
-              val[2 % C] = s2 * ((a2 << 1) + (m & 1));
-            } else if (maxcand == 3) {
-              const int p1 = m ? 1 : 0;
-              val[1 % C] = s1 * ((a1 << 1) + p1);
-              if (p1)
-                val[2 % C] = s2 * ((a2 << 1) + (m - p1));
-            } else if (maxcand == 2) {
-              val[1 % C] = s1 * ((a1 << 1) + m);
-            }
-          }
-        }
+        pred_point<C, ENC>(
+          cx, ENC ? cx.rm + (size_t)i * 6 : nullptr, cnt, nbv, nwt, col, q, wgt, icpc, maxcand, clip_max, val, myrec);
         {
           const u32x4 st = {(uint32_t)myrec[0], (uint32_t)myrec[1 % C], (uint32_t)myrec[2 % C], cx.tag};
           __builtin_amdgcn_raw_buffer_store_b128(st, rsrc, i * 16, 0, /*sc1*/ 16);
@@ -957,6 +1016,262 @@ pred_dag_kernel(PredCtx cx)
         __builtin_amdgcn_s_sleep(1);
       }
     }
+  }
+}
+
+// ---- the encoder's finish: an ordered walk over what the passes left undecided --------------
+// The passes above remove almost every wrong decision within a few rounds; after that a pass
+// recomputes the whole slice to move the first wrong decision a few dozen predictors ahead, and
+// whether it ever stops is chance.  What a pass leaves behind is enough to finish exactly.  Let V'
+// be the values of the pass before the last, R (cx.rm) the trajectory computed from V', V the last
+// pass's values and D = { i : V_i != V'_i } in ascending order.  Everything is causal in coding
+// order, so on [0, min D) V is the sequential coder's result, and R at d = min D is the exact
+// state in front of d.  pred_walk_kernel takes it from there: ONE wavefront walks the predictors
+// in coding order from d with the state in registers, pred_point per predictor, and compares as
+// it goes.  Once the state behind a predictor equals R's (all 2C words) and the next predictor
+// is not in D, everything ahead up to the next element of D is the sequential coder's as well
+// (same state, same values, so the same recurrence) -- PROVIDED its neighbours' reconstructions
+// are the pass's.  The walk marks every predictor whose reconstruction it changed (w.changed),
+// and from a point of agreement it looks ahead, 256 predictors per step across the lanes, for the
+// first predictor that is in D or has a marked neighbour; before it has changed a reconstruction
+// that is simply the next element of D.  The walk resumes there with R's state, which is exact
+// there by the same induction.  It ends at n: every value, every reconstruction and both
+// reconstruction copies (attrs, rec) are then the sequential coder's.  No polling, no wait on
+// another workgroup; every loop is bounded by n.
+struct PredWalk {
+  const int32_t* rank;  // [n + 1] rank[i] = elements of D below i (inclusive scan of the flags)
+  const int32_t* list;  // [rank[n]] D, ascending
+  uint8_t* changed;     // [n] cleared; 1 where the walk changed a reconstruction
+  int32_t* out;         // [4] predictors walked, stretches walked, longest stretch, 1 = reached n
+};
+
+// flags for the scan: rank[i + 1] = (predictor i's values differ from the previous pass's);
+// prev == nullptr (after the very first pass there is nothing to compare with): every predictor
+__global__ __launch_bounds__(256) void
+pred_diff_flags_kernel(
+  const int32_t* __restrict__ values, const int32_t* __restrict__ prev, int n, int c, int32_t* __restrict__ rank)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool diff = !prev;
+    if (prev)
+      for (int k = 0; k < c; k++)
+        diff |= values[(size_t)i * c + k] != prev[(size_t)i * c + k];
+    rank[i + 1] = diff;
+    if (i == 0)
+      rank[0] = 0;
+  }
+}
+
+// after the inclusive scan: D as a list
+__global__ __launch_bounds__(256) void
+pred_diff_list_kernel(const int32_t* __restrict__ rank, int n, int32_t* __restrict__ list)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    if (rank[i + 1] != rank[i])
+      list[rank[i]] = i;
+}
+
+constexpr int kWalkBlock = 64;  // predictors staged in LDS per refill
+constexpr int kWalkAhead = 4;   // look-ahead: this many wavefront-wide groups per step
+
+template<int C, bool INTER>
+__global__ __launch_bounds__(64) void
+pred_walk_kernel(PredCtx cx, PredWalk w)
+{
+  // the records of predictors [i0, i0 + 64): everything a step reads except the log2 table
+  __shared__ int32_t s_cnt[kWalkBlock], s_pt[kWalkBlock], s_ni[kWalkBlock][3], s_nw[kWalkBlock][3];
+  __shared__ int32_t s_col[kWalkBlock][3], s_old[kWalkBlock][3], s_val[kWalkBlock][3], s_nb[kWalkBlock][3][3];
+  __shared__ int32_t s_rec[kWalkBlock][3], s_rm[kWalkBlock + 1][6], s_in_d[kWalkBlock + 1];
+  __shared__ int32_t s_next[4];
+  __shared__ Quantizer s_q[kWalkBlock][2];
+  __shared__ int64_t s_wgt[kWalkBlock][2];
+  __shared__ int8_t s_icp[kWalkBlock][3];
+  const int lane = threadIdx.x;
+  const int n = cx.n;
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(cx.rec, 0, (int)((size_t)n * 16), 0x00020000);
+  const int maxcand = cx.max_direct + !cx.avg_disabled;
+  const int64_t clip_max = ((int64_t)1 << cx.bitdepth) - 1;
+  const int total = w.rank[n];
+  int i0 = total > 0 ? w.list[0] : n;
+  int32_t st[6] = {0, 0, 0, 0, 0, 0};  // (lane 0's: the state in front of the predictor the walk stands at)
+  bool fresh = true;                   // the state is to be taken from R
+  int dirty = 0;                       // the walk has changed a reconstruction
+  int walked = 0, stretches = 0, longest = 0, run = 0;
+  while (i0 < n) {
+    // what this wavefront stored (reconstructions, marks) is read back below: complete the stores first
+    __threadfence();
+    {
+      const int i = i0 + lane;
+      const bool live = i < n;
+      int cnt = 0, pt = 0;
+      if (live) {
+        cnt = cx.nc[i];
+        pt = cx.indexes[i];
+        const int r = pred_range_of(cx, i);
+        const int layer = cx.range_qlayer[r];
+        const int o0 = cx.qp_off ? cx.qp_off[2 * (size_t)pt] : 0;
+        const int o1 = cx.qp_off ? cx.qp_off[2 * (size_t)pt + 1] : 0;
+        const int qp0 = clip(cx.layer_qp[layer][0] + o0, 4, cx.max_qp);
+        const int qp1 = clip(cx.layer_qp[layer][1] + o1 + qp0, 4, cx.max_qp);
+        const int64_t qw = (int64_t)cx.qw[i];
+        const Quantizer q0 = make_quantizer(qp0), q1 = make_quantizer(qp1);
+        s_q[lane][0] = q0;
+        s_q[lane][1] = q1;
+        s_wgt[lane][0] = (qw < q0.step ? qw : (int64_t)q0.step) >> 8;
+        s_wgt[lane][1] = (qw < q1.step ? qw : (int64_t)q1.step) >> 8;
+        for (int k = 0; k < 3; k++)
+          s_icp[lane][k] = C == 3 && cx.icp_enabled ? cx.icp[3 * cx.range_lod[r] + k] : 0;
+        u32x4 g[3];
+        for (int j = 0; j < 3; j++) {
+          const int nb = j < cnt ? cx.ni[3 * (size_t)i + j] : 0;
+          s_ni[lane][j] = nb;
+          s_nw[lane][j] = j < cnt ? cx.nw[3 * (size_t)i + j] : 0;
+          g[j] = u32x4{0, 0, 0, 0};
+          if (j < cnt && INTER && nb >= n)
+            g[j].x = (uint32_t)cx.frame_attr[nb - n];
+          else if (j < cnt && nb < i0)
+            g[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, nb * 16, 0, /*sc1*/ 16);
+        }
+        for (int j = 0; j < 3; j++) {
+          s_nb[lane][j][0] = (int32_t)g[j].x;
+          s_nb[lane][j][1] = (int32_t)g[j].y;
+          s_nb[lane][j][2] = (int32_t)g[j].z;
+        }
+        for (int k = 0; k < 3; k++) {
+          s_col[lane][k] = k < C ? cx.src[(size_t)pt * C + k] : 0;
+          s_old[lane][k] = k < C ? cx.attrs[(size_t)pt * C + k] : 0;
+          s_val[lane][k] = k < C ? cx.values[(size_t)i * C + k] : 0;
+        }
+        for (int k = 0; k < 6; k++)
+          s_rm[lane][k] = cx.rm[(size_t)i * 6 + k];
+        s_in_d[lane] = w.rank[i + 1] != w.rank[i];
+      }
+      s_cnt[lane] = cnt;
+      s_pt[lane] = pt;
+      if (lane == 0) {
+        const int e = i0 + kWalkBlock;
+        s_in_d[kWalkBlock] = e < n ? w.rank[e + 1] != w.rank[e] : 0;
+        for (int k = 0; k < 6; k++)
+          s_rm[kWalkBlock][k] = e < n ? cx.rm[(size_t)e * 6 + k] : 0;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- the walk through the block: one lane, the state in its registers ----
+    if (lane == 0) {
+      int next = i0 + kWalkBlock < n ? i0 + kWalkBlock : n, seek = 0;
+      for (int t = 0; t < kWalkBlock && i0 + t < n; t++) {
+        const int i = i0 + t;
+        if (fresh) {
+          for (int k = 0; k < 6; k++)
+            st[k] = s_rm[t][k];
+          fresh = false;
+          stretches++;
+          run = 0;
+        }
+        const int cnt = s_cnt[t], pt = s_pt[t];
+        int32_t nbv[3][C];
+        int32_t nwt[3], col[3], val[3] = {0, 0, 0}, myrec[C];
+        int8_t icpc[3];
+        for (int j = 0; j < 3; j++) {
+          const int nb = s_ni[t][j];
+          const bool mine = j < cnt && nb >= i0 && (!INTER || nb < n);  // walked in this block
+          for (int k = 0; k < C; k++)
+            nbv[j][k] = j < cnt ? (mine ? s_rec[nb - i0][k] : s_nb[t][j][k]) : 0;
+          nwt[j] = s_nw[t][j];
+          col[j] = s_col[t][j];
+          icpc[j] = s_icp[t][j];
+        }
+        const Quantizer q[2] = {s_q[t][0], s_q[t][1]};
+        const int64_t wgt[2] = {s_wgt[t][0], s_wgt[t][1]};
+        pred_point<C, true>(cx, st, cnt, nbv, nwt, col, q, wgt, icpc, maxcand, clip_max, val, myrec);
+        bool rchg = false;
+        for (int k = 0; k < C; k++) {
+          rchg |= myrec[k] != s_old[t][k];
+          s_rec[t][k] = myrec[k];
+          cx.attrs[(size_t)pt * C + k] = myrec[k];
+          cx.values[(size_t)i * C + k] = val[k];
+        }
+        {
+          const u32x4 gr = {(uint32_t)myrec[0], (uint32_t)myrec[1 % C], (uint32_t)myrec[2 % C], cx.tag};
+          __builtin_amdgcn_raw_buffer_store_b128(gr, rsrc, i * 16, 0, /*sc1*/ 16);
+        }
+        if (rchg) {
+          w.changed[i] = 1;
+          dirty = 1;
+        }
+        // resStatUpdate
+        bool same = true;
+        for (int k = 0; k < C; k++) {
+          st[k] = pred_rate_step(st[k], val[k] != 0);
+          if (val[k])
+            st[3 + k] = pred_rate_step(st[3 + k], (val[k] < 0 ? -val[k] : val[k]) > 1);
+          same &= st[k] == s_rm[t + 1][k] && st[3 + k] == s_rm[t + 1][3 + k];
+        }
+        walked++;
+        run++;
+        longest = run > longest ? run : longest;
+        if (i + 1 < n && same && !s_in_d[t + 1]) {
+          next = i + 1;
+          seek = 1;
+          break;
+        }
+      }
+      s_next[0] = next;
+      s_next[1] = seek;
+      s_next[2] = dirty;
+    }
+    __builtin_amdgcn_wave_barrier();
+    i0 = s_next[0];
+    const int seek = s_next[1], any_dirty = s_next[2];
+    __builtin_amdgcn_wave_barrier();
+    if (!seek)
+      continue;
+    // ---- agreement at i0: the first predictor at or behind it that has to be walked ----
+    fresh = true;
+    const int r0 = w.rank[i0];
+    const int next_d = r0 < total ? w.list[r0] : n;
+    if (!any_dirty) {
+      i0 = next_d;
+      continue;
+    }
+    __threadfence();  // (the marks)
+    int found = next_d;
+    for (int b = i0; b < next_d; b += 64 * kWalkAhead) {
+      int cnt[kWalkAhead], nb[kWalkAhead][3];
+#pragma unroll
+      for (int u = 0; u < kWalkAhead; u++) {
+        const int i = b + u * 64 + lane;
+        cnt[u] = i < next_d ? cx.nc[i] : 0;
+        for (int j = 0; j < 3; j++)
+          nb[u][j] = i < next_d ? cx.ni[3 * (size_t)i + j] : 0;
+      }
+      int hit[kWalkAhead];
+#pragma unroll
+      for (int u = 0; u < kWalkAhead; u++) {
+        hit[u] = 0;
+        for (int j = 0; j < 3; j++)
+          if (j < cnt[u] && nb[u][j] < n)
+            hit[u] |= w.changed[nb[u][j]];
+      }
+      int first = -1;
+#pragma unroll
+      for (int u = 0; u < kWalkAhead; u++) {
+        const unsigned long long m = __ballot(hit[u] != 0);
+        if (first < 0 && m)
+          first = b + u * 64 + __ffsll((long long)m) - 1;
+      }
+      if (first >= 0) {
+        found = first;
+        break;
+      }
+    }
+    i0 = found;
+  }
+  if (lane == 0) {
+    w.out[0] = walked;
+    w.out[1] = stretches;
+    w.out[2] = longest;
+    w.out[3] = 1;
   }
 }
 

@@ -64,6 +64,13 @@ class Context:
         _lib.check(self._lib.gpcc_ctx_pred_pass_stats(self._h, out))
         return dict(zip(("slices", "passes", "most_passes", "declined_at_the_limit"), (int(v) for v in out)))
 
+    def pred_repair_stats(self):
+        """{slices, walked, stretches, longest_stretch} of the predicting encoder's ordered walk (the finish of
+        slices whose passes do not settle) since the context was created"""
+        out = (C.c_int64 * 4)()
+        _lib.check(self._lib.gpcc_ctx_pred_repair_stats(self._h, out))
+        return dict(zip(("slices", "walked", "stretches", "longest_stretch"), (int(v) for v in out)))
+
     def set_profiling(self, on):
         _lib.check(self._lib.gpcc_ctx_set_profiling(self._h, int(bool(on))))
 

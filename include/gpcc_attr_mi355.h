@@ -276,6 +276,52 @@ int gpcc_dev_attr_morton_sort(
   const void* d_xyz, void* d_morton, void* d_order);
 
 /* ------------------------------------------------------------------ */
+/* attribute positions in the pseudo-spherical domain (aps.spherical_coord_flag) */
+
+/* What the reference does to a slice's positions in front of attrEncoder->encode / _attrDecoder->decode
+ * (encoder.cpp:1148-1197, decoder.cpp:871-920): convertXyzToRpl (coordinate_conversion.cpp:44-69; findLaser
+ * geometry_octree.cpp:856-872, isqrt / iatan2 misc.cpp:139-147, 279-309), the bounding box of the result, and
+ * offsetAndScale (coordinate_conversion.cpp:109-118) by the box's minimum and attr_coord_scale.  The result is
+ * what gpcc_attr_morton_sort, gpcc_lod_build and the gpcc_*_attr entries take as xyz.
+ *
+ * Domain: every coordinate less than 2^22 away from laser_origin, every scaled result in [0, 2^21).  A point
+ * outside it makes the call (host tier) or the next gpcc_ctx_synchronize (device tier) fail with
+ * GPCC_ERR_INVALID_ARG.
+ *
+ * Not covered, left to the caller's host code: offsetAndScaleShift of the reference frame
+ * (coordinate_conversion.cpp:122-144, a few lines over another cloud), the encoder's choice of the scale
+ * (normalisedAxesWeights, :73-105) and the second reference of bi-prediction. */
+#define GPCC_MAX_LASERS 128 /* cfg/sequences-cat3.yaml lists at most 64 lasersTheta; more -> GPCC_ERR_UNSUPPORTED */
+
+typedef struct gpcc_spherical_params {
+  int32_t laser_origin[3];            /* GeometryBrickHeader::geomAngularOrigin(gps) */
+  int32_t num_lasers;                 /* gps.angularTheta.size(), >= 1 */
+  int32_t laser_theta[GPCC_MAX_LASERS]; /* gps.angularTheta, ascending */
+  int32_t attr_coord_scale[3];        /* AttributeParameterSet::attr_coord_scale */
+  int32_t min_pos_mode;               /* 0: the bounding box's minimum (intra, encoder.cpp:1186-1188)
+                                         1: min_pos as given (zero when aps.attrInterPredictionEnabled; or
+                                            the caller's own)
+                                         2: min(bounding box's minimum, min_pos) per component
+                                            (predgeom + inter, encoder.cpp:1165-1166) */
+  int32_t min_pos[3];
+  int32_t convert;                    /* 1: xyz -> (r, phi, laser) first; 0: the input is already spherical
+                                         (predgeom's _posSph, encoder.cpp:1158-1160): bounding box, offset
+                                         and scale only */
+} gpcc_spherical_params;
+
+/* Host tier, synchronous.  xyz, pos_out int32 [n][3] (pos_out may be xyz); bbox [6]: min, max of the UNSCALED
+ * (r, phi, laser), may be NULL.  On failure neither pos_out nor bbox has been written. */
+int gpcc_attr_to_spherical(
+  gpcc_ctx* ctx, const gpcc_spherical_params* params, const int32_t* xyz, int32_t n, int32_t* pos_out,
+  int32_t* bbox);
+
+/* Device tier: enqueues on the context's stream and returns.  Every slice of the batch gets its own bounding box
+ * and minimum.  d_xyz, d_pos_out int32 [n][3], equal or disjoint; d_bbox int32 [num_slices][6], may be NULL. */
+int gpcc_dev_attr_to_spherical(
+  gpcc_ctx* ctx, const gpcc_spherical_params* params, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_pos_out, void* d_bbox);
+
+/* ------------------------------------------------------------------ */
 /* lifting transform (predictors given)                                 */
 
 #define GPCC_MAX_LODS 32

@@ -3,7 +3,7 @@ if the HIP library is missing or a call fails this module raises."""
 import ctypes as C
 import os
 
-from .params import LiftParams, LodParams, PredParams, RahtParams
+from .params import LiftParams, LodParams, PredParams, RahtParams, SphericalParams
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GPCC_LIB_PATH: an experiment build of the same library (tools/, parameter sweeps)
@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "gpcc_lod_build_partial", "gpcc_lift_inverse_partial", "gpcc_lift_decode_attr_partial",
     "gpcc_dev_lift_decode_attr_partial",
     "gpcc_lift_encode_attr_rdo", "gpcc_pred_encode_attr_rdo", "gpcc_slice_rdo_choose",
+    "gpcc_attr_to_spherical", "gpcc_dev_attr_to_spherical",
     "gpcc_ctx_reserve",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_guard_selftest",
@@ -149,6 +150,9 @@ def load():
                                               i32, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gpcc_slice_rdo_choose.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, C.POINTER(i32),
                                           C.POINTER(C.c_double)]
+    # attribute positions in the pseudo-spherical domain (spherical_coord_flag)
+    lib.gpcc_attr_to_spherical.argtypes = [vp, C.POINTER(SphericalParams), vp, i32, vp, vp]
+    lib.gpcc_dev_attr_to_spherical.argtypes = [vp, C.POINTER(SphericalParams), i32, i64p, vp, vp, vp]
     lib.gpcc_multi_create.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
     lib.gpcc_multi_destroy.argtypes = [vp]
     lib.gpcc_multi_destroy.restype = None

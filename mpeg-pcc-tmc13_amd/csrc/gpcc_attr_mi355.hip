@@ -52,6 +52,7 @@
 #include "residual_bins.hpp"
 #include "recolour_kernels.hpp"
 #include "slice_rdo.hpp"
+#include "spherical.hpp"
 
 using namespace gpcc;
 
@@ -1315,6 +1316,11 @@ check_device_error(gpcc_ctx* ctx)
       return fail(
         GPCC_ERR_UNSUPPORTED,
         "inter-frame RAHT: a coefficient magnitude beyond the rate estimate's log2 table; nothing was written");
+    if (code == kRplErrorDomain)
+      return fail(
+        GPCC_ERR_INVALID_ARG,
+        "spherical attribute positions: a point outside the domain (a coordinate 2^22 or more away from the laser "
+        "origin, or a scaled coordinate outside [0, 2^21)); the result is invalid");
     if (code == 2)
       return fail(
         GPCC_ERR_INVALID_ARG,
@@ -4926,6 +4932,166 @@ gpcc_estimate_dist2(
   int32_t search_range, float percentile, int32_t* shift_bits)
 {
   return counted(ctx, estimate_dist2(ctx, xyz, n, sampling_period, search_range, percentile, shift_bits), n);
+}
+
+}  // extern "C"
+
+// ---- attribute positions in the pseudo-spherical domain (spherical.hpp) -------------------------
+namespace {
+
+// what can be refused without a context
+int
+check_spherical_params(const gpcc_spherical_params* sp)
+{
+  if (!sp)
+    return fail(GPCC_ERR_INVALID_ARG, "spherical params is null");
+  if (sp->num_lasers < 1)
+    return fail(GPCC_ERR_INVALID_ARG, "num_lasers < 1");
+  if (sp->num_lasers > GPCC_MAX_LASERS)
+    return fail(GPCC_ERR_UNSUPPORTED, "more than GPCC_MAX_LASERS lasers: the slice stays on the reference CPU path");
+  for (int i = 1; i < sp->num_lasers; i++)
+    if (sp->laser_theta[i] < sp->laser_theta[i - 1])
+      return fail(GPCC_ERR_INVALID_ARG, "laser_theta is not ascending");
+  if (sp->min_pos_mode < 0 || sp->min_pos_mode > 2)
+    return fail(GPCC_ERR_INVALID_ARG, "unknown min_pos_mode");
+  if (sp->convert != 0 && sp->convert != 1)
+    return fail(GPCC_ERR_INVALID_ARG, "convert must be 0 or 1");
+  return GPCC_OK;
+}
+
+// enqueues on the context's stream and returns; d_pos_out == d_xyz is allowed
+int
+dev_to_spherical(
+  gpcc_ctx* ctx, const gpcc_spherical_params* sp, int32_t num_slices, const int64_t* offsets, const void* d_xyz,
+  void* d_pos_out, void* d_bbox)
+{
+  int r = check_spherical_params(sp);
+  if (r)
+    return r;
+  if (!d_xyz || !d_pos_out)
+    return fail(GPCC_ERR_INVALID_ARG, "null device buffer");
+  // (the slice table ahead of the context, like every other argument)
+  if (num_slices < 1 || !offsets || offsets[0] != 0)
+    return fail(GPCC_ERR_INVALID_ARG, "bad slice offsets");
+  for (int i = 0; i < num_slices; i++)
+    if (offsets[i + 1] <= offsets[i])
+      return fail(GPCC_ERR_INVALID_ARG, "empty or unordered slice");
+  if (offsets[num_slices] > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per batch");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  // tiles never straddle a slice (spherical.hpp RplArgs)
+  std::vector<int32_t> meta(2 * ((size_t)num_slices + 1));
+  int32_t* h_pt = meta.data();
+  int32_t* h_tile = meta.data() + num_slices + 1;
+  h_tile[0] = 0;
+  for (int s = 0; s <= num_slices; s++)
+    h_pt[s] = (int32_t)offsets[s];
+  for (int s = 0; s < num_slices; s++)
+    h_tile[s + 1] = h_tile[s] + rpl_tiles(offsets[s + 1] - offsets[s]);
+
+  Arena measure;
+  measure.take<int32_t>(meta.size());
+  measure.take<int32_t>(6 * (size_t)num_slices);
+  r = ensure_arena(ctx, measure.used);
+  if (r)
+    return r;
+  Arena& ar = ctx->arena;
+  ar.reset();
+  int32_t* d_meta = ar.take<int32_t>(meta.size());
+  int32_t* d_box = ar.take<int32_t>(6 * (size_t)num_slices);
+  HIP_TRY(h2d_user(ctx, d_meta, meta.data(), meta.size() * sizeof(int32_t), st));
+
+  RplArgs a{};
+  a.src = (const int32_t*)d_xyz;
+  a.dst = (int32_t*)d_pos_out;
+  a.bbox = d_bbox ? (int32_t*)d_bbox : d_box;
+  a.pt_off = d_meta;
+  a.tile_off = d_meta + num_slices + 1;
+  a.error = ctx->d_error;
+  a.num_slices = num_slices;
+  a.num_tiles = h_tile[num_slices];
+  a.num_lasers = sp->num_lasers;
+  a.min_pos_mode = sp->min_pos_mode;
+  for (int k = 0; k < 3; k++) {
+    a.origin[k] = sp->laser_origin[k];
+    a.scale[k] = sp->attr_coord_scale[k];
+    a.min_pos[k] = sp->min_pos[k];
+  }
+  for (int i = 0; i < sp->num_lasers; i++)
+    a.theta[i] = sp->laser_theta[i];
+  HIP_TRY(rpl_launch(st, a, sp->convert != 0, [&](const char* name) { return Timer(ctx, name); }));
+  if (ctx->h_error)
+    HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  return GPCC_OK;
+}
+
+// synchronous; the caller's buffers are written only when the whole call has succeeded
+int
+host_to_spherical(
+  gpcc_ctx* ctx, const gpcc_spherical_params* sp, const int32_t* xyz, int32_t n, int32_t* pos_out, int32_t* bbox)
+{
+  int r = check_spherical_params(sp);
+  if (r)
+    return r;
+  if (!xyz || !pos_out || n <= 0)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer or n <= 0");
+  if (n > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per call");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  int32_t* d_pos = nullptr;
+  int32_t* d_box = nullptr;
+  auto run = [&]() -> int {
+    HIP_TRY(pool_malloc(ctx, (void**)&d_pos, sizeof(int32_t) * 3 * n));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_box, sizeof(int32_t) * 6));
+    HIP_TRY(h2d_user(ctx, d_pos, xyz, sizeof(int32_t) * 3 * n, st));
+    const int64_t offs[2] = {0, n};
+    int r = dev_to_spherical(ctx, sp, 1, offs, d_pos, d_pos, d_box);
+    if (r)
+      return r;
+    HIP_TRY(small_reset(ctx));
+    int32_t* h_box = (int32_t*)small_slot(ctx, sizeof(int32_t) * 6);
+    HIP_TRY(hipMemcpyAsync(h_box, d_box, sizeof(int32_t) * 6, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    r = check_device_error(ctx);
+    if (r)
+      return r;
+    HIP_TRY(d2h_user(ctx, pos_out, d_pos, sizeof(int32_t) * 3 * n, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bbox)
+      memcpy(bbox, h_box, sizeof(int32_t) * 6);
+    return GPCC_OK;
+  };
+  r = run();
+  pool_free(ctx, d_pos);
+  pool_free(ctx, d_box);
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int
+gpcc_attr_to_spherical(
+  gpcc_ctx* ctx, const gpcc_spherical_params* params, const int32_t* xyz, int32_t n, int32_t* pos_out, int32_t* bbox)
+{
+  return counted(ctx, host_to_spherical(ctx, params, xyz, n, pos_out, bbox), n);
+}
+
+int
+gpcc_dev_attr_to_spherical(
+  gpcc_ctx* ctx, const gpcc_spherical_params* params, int32_t num_slices, const int64_t* offsets, const void* d_xyz,
+  void* d_pos_out, void* d_bbox)
+{
+  return counted(
+    ctx, dev_to_spherical(ctx, params, num_slices, offsets, d_xyz, d_pos_out, d_bbox), batch_points(offsets, num_slices));
 }
 
 }  // extern "C"

@@ -219,6 +219,94 @@ GPCC_HD uint32_t isqrt(uint64_t x, const RsqrtLut& lut)
   return (uint32_t)(1 + ((x0 * irsqrt(x0, lut)) >> 32));
 }
 
+// ---- arc tangent (tmc3/misc.cpp:230-309) --------------------------------
+// Normative arcsine look-up table of the fixed-point iatan2: 20-bit angles at
+// sine steps of 2^-9, the last entry repeated.  Like RsqrtLut it may live in
+// LDS (device) or in host memory.
+constexpr int kAsinLutSize = 364;
+struct AsinLut {
+  uint32_t v[kAsinLutSize];
+};
+
+#define GPCC_ASIN_LUT                                                         \
+  0, 2048, 4096, 6144, 8192, 10240, 12288, 14336, 16385, 18433, 20481,        \
+    22530, 24578, 26627, 28676, 30724, 32773, 34822, 36872, 38921, 40970,     \
+    43020, 45070, 47120, 49170, 51220, 53271, 55322, 57373, 59424, 61475,     \
+    63527, 65579, 67631, 69683, 71736, 73789, 75842, 77896, 79949, 82004,     \
+    84058, 86113, 88168, 90223, 92279, 94335, 96392, 98449, 100506,           \
+    102563, 104621, 106680, 108739, 110798, 112858, 114918, 116978,           \
+    119040, 121101, 123163, 125225, 127288, 129352, 131416, 133480,           \
+    135545, 137611, 139677, 141743, 143810, 145878, 147946, 150015,           \
+    152085, 154155, 156225, 158297, 160368, 162441, 164514, 166588,           \
+    168662, 170737, 172813, 174890, 176967, 179045, 181123, 183203,           \
+    185283, 187363, 189445, 191527, 193610, 195694, 197779, 199864,           \
+    201950, 204037, 206125, 208214, 210303, 212393, 214485, 216577,           \
+    218669, 220763, 222858, 224954, 227050, 229148, 231246, 233345,           \
+    235445, 237547, 239649, 241752, 243856, 245961, 248068, 250175,           \
+    252283, 254392, 256502, 258614, 260726, 262840, 264954, 267070,           \
+    269187, 271305, 273424, 275544, 277666, 279788, 281912, 284037,           \
+    286163, 288290, 290419, 292549, 294680, 296812, 298945, 301080,           \
+    303216, 305354, 307492, 309632, 311773, 313916, 316060, 318206,           \
+    320352, 322500, 324650, 326801, 328953, 331107, 333262, 335419,           \
+    337577, 339737, 341898, 344061, 346225, 348391, 350558, 352727,           \
+    354897, 357069, 359243, 361418, 363595, 365773, 367953, 370135,           \
+    372318, 374503, 376690, 378879, 381069, 383261, 385455, 387650,           \
+    389847, 392046, 394247, 396450, 398655, 400861, 403069, 405279,           \
+    407491, 409705, 411921, 414139, 416359, 418581, 420804, 423030,           \
+    425258, 427488, 429720, 431954, 434190, 436428, 438668, 440910,           \
+    443155, 445401, 447650, 449901, 452155, 454410, 456668, 458928,           \
+    461190, 463455, 465722, 467991, 470262, 472536, 474813, 477091,           \
+    479373, 481656, 483942, 486231, 488522, 490815, 493111, 495410,           \
+    497711, 500015, 502322, 504631, 506943, 509257, 511574, 513894,           \
+    516217, 518542, 520870, 523201, 525535, 527872, 530211, 532553,           \
+    534899, 537247, 539598, 541952, 544310, 546670, 549033, 551399,           \
+    553769, 556142, 558517, 560896, 563278, 565664, 568052, 570444,           \
+    572839, 575238, 577640, 580045, 582454, 584866, 587282, 589701,           \
+    592123, 594549, 596979, 599412, 601849, 604290, 606734, 609183,           \
+    611634, 614090, 616549, 619013, 621480, 623951, 626426, 628905,           \
+    631388, 633875, 636366, 638862, 641361, 643865, 646373, 648885,           \
+    651401, 653922, 656447, 658976, 661510, 664049, 666592, 669139,           \
+    671691, 674248, 676809, 679375, 681946, 684522, 687103, 689688,           \
+    692278, 694874, 697474, 700080, 702690, 705306, 707927, 710553,           \
+    713184, 715821, 718463, 721111, 723764, 726423, 729087, 731757,           \
+    734433, 737115, 739802, 742495, 745194, 747899, 750611, 753328,           \
+    756051, 758781, 761517, 764259, 767008, 769763, 772525, 775294,           \
+    778069, 780850, 783639, 786435, 789237, 792047, 794863, 797687,           \
+    800518, 803357, 806202, 809056, 811917, 814785, 817662, 820546,           \
+    823438, 823438
+
+// iatan2Core (tmc3/misc.cpp:278-293) for 0 <= y <= x with the reciprocal
+// square root given: rinv == irsqrt(x^2 + y^2).  The sine y / sqrt(x^2 + y^2)
+// is at most 2^-1/2, so the table index stays below 363.
+GPCC_HD int iatan2_core(int y, int x, uint64_t rinv, const AsinLut& lut)
+{
+  if (x == 0)
+    return 0;
+  const int r = (int)(((uint64_t)y * rinv) >> 20);  // 40 - 20 = 20 bits precision
+  const int idx = r >> 11;
+  const int lambda = r - (idx << 11);
+  const int a0 = (int)lut.v[idx], a1 = (int)lut.v[idx + 1];
+  return a0 + ((lambda * (a1 - a0)) >> 11);
+}
+
+// iatan2 (tmc3/misc.cpp:297-309) with rinv == irsqrt(x^2 + y^2): the sum of
+// the squares does not depend on the signs or the order of the two arguments,
+// so one reciprocal square root serves both branches.
+GPCC_HD int iatan2(int y, int x, uint64_t rinv, const AsinLut& lut)
+{
+  const int xa = x < 0 ? -x : x;
+  const int ya = y < 0 ? -y : y;
+  int t = ya <= xa ? iatan2_core(ya, xa, rinv, lut) : 1647099 - iatan2_core(xa, ya, rinv, lut);
+  if (x < 0)
+    t = 3294199 - t;  // pi - atan
+  return y < 0 ? -t : t;
+}
+
+GPCC_HD int iatan2(int y, int x, const RsqrtLut& rs, const AsinLut& lut)
+{
+  return iatan2(y, x, irsqrt((uint64_t)((int64_t)x * x) + (uint64_t)((int64_t)y * y), rs), lut);
+}
+
 // ---- quantiser (tmc3/quantization.h:79-102, quantization.cpp:46-52) ---
 struct Quantizer {
   int32_t step;

@@ -312,3 +312,38 @@ def recolour_params(bitdepth=8, search_range=1, k_fwd=8, k_bwd=1, weighted_fwd=T
     p.skip_avg_if_identical_fwd, p.skip_avg_if_identical_bwd = int(skip_fwd), int(skip_bwd)
     p.bitdepth = bitdepth
     return p
+
+
+GPCC_MAX_LASERS = 128
+
+
+class SphericalParams(C.Structure):
+    """ctypes mirror of gpcc_spherical_params: what encoder.cpp:1148-1197 / decoder.cpp:871-920 read when they
+    move a slice's positions into the pseudo-spherical domain."""
+    _fields_ = [
+        ("laser_origin", C.c_int32 * 3),
+        ("num_lasers", C.c_int32),
+        ("laser_theta", C.c_int32 * GPCC_MAX_LASERS),
+        ("attr_coord_scale", C.c_int32 * 3),
+        ("min_pos_mode", C.c_int32),   # 0 bounding box's minimum, 1 min_pos, 2 the smaller of the two
+        ("min_pos", C.c_int32 * 3),
+        ("convert", C.c_int32),        # 0: the input is (r, phi, laser) already
+    ]
+
+
+def spherical_params(origin, thetas, scale, min_pos_mode=0, min_pos=(0, 0, 0), convert=True):
+    """origin: geomAngularOrigin; thetas: gps.angularTheta, ascending (round(tan(elevation) * 2^18));
+    scale: aps.attr_coord_scale."""
+    p = SphericalParams()
+    if len(thetas) > GPCC_MAX_LASERS:
+        raise ValueError(f"more than {GPCC_MAX_LASERS} lasers")
+    p.num_lasers = len(thetas)
+    for i, v in enumerate(thetas):
+        p.laser_theta[i] = int(v)
+    for k in range(3):
+        p.laser_origin[k] = int(origin[k])
+        p.attr_coord_scale[k] = int(scale[k])
+        p.min_pos[k] = int(min_pos[k])
+    p.min_pos_mode = int(min_pos_mode)
+    p.convert = int(bool(convert))
+    return p

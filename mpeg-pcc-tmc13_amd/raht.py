@@ -172,6 +172,31 @@ class Context:
             self._h, C.byref(params), len(offsets) - 1, off, C.c_void_p(d_morton),
             C.c_void_p(d_qp_off or 0), C.c_void_p(d_attrs), C.c_void_p(d_coeffs), c))
 
+    def dev_attr_morton_sort(self, offsets, d_xyz, d_morton, d_order):
+        """gpcc_dev_attr_morton_sort: Morton codes and the stable order of every slice (indices local to the slice)"""
+        off = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        _lib.check(self._lib.gpcc_dev_attr_morton_sort(
+            self._h, len(offsets) - 1, off, C.c_void_p(d_xyz), C.c_void_p(d_morton), C.c_void_p(d_order)))
+
+    # ---- attribute positions in the pseudo-spherical domain --------------
+    def attr_to_spherical(self, params, xyz, out=None):
+        """gpcc_attr_to_spherical -> (positions int32 [n, 3], bounding box int32 [2, 3] of the unscaled
+        (r, phi, laser)).  out: where the positions go (xyz itself for the in-place form)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        n = xyz.shape[0]
+        pos = np.zeros((n, 3), dtype=np.int32) if out is None else out
+        bbox = np.zeros((2, 3), dtype=np.int32)
+        _lib.check(self._lib.gpcc_attr_to_spherical(
+            self._h, C.byref(params), xyz.ctypes.data, n, pos.ctypes.data, bbox.ctypes.data))
+        return pos, bbox
+
+    def dev_attr_to_spherical(self, params, offsets, d_xyz, d_pos_out, d_bbox=None):
+        """gpcc_dev_attr_to_spherical: enqueued on the context's stream; d_pos_out may be d_xyz"""
+        off = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        _lib.check(self._lib.gpcc_dev_attr_to_spherical(
+            self._h, C.byref(params), len(offsets) - 1, off, C.c_void_p(d_xyz), C.c_void_p(d_pos_out),
+            C.c_void_p(d_bbox or 0)))
+
     # ---- lifting transform (predictors given, host tier) -------------------
     @staticmethod
     def _partial(min_geom_node_size_log2, geom_num_points, n):

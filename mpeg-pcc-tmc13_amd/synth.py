@@ -114,6 +114,18 @@ def lidar_cloud(n, seed=1, bits=18, rings=64, bitdepth=8, dedup=True, refl_noise
     return np.ascontiguousarray(xyz), np.ascontiguousarray(refl.reshape(-1, 1))
 
 
+def lidar_lasers(bits=18, rings=64):
+    """The laser origin and the ascending table of round(tan(elevation) * 2^18) that belong to lidar_cloud's
+    rings and grid: what a geometry parameter set would carry for such a frame (geomAngularOrigin,
+    angularTheta).  -> (origin int32 [3], thetas int32 [rings])"""
+    side = float((1 << bits) - 1)
+    ring = np.arange(rings)
+    elev = np.deg2rad(-24.8 + 26.8 * ring / max(1, rings - 1))
+    thetas = np.rint(np.tan(elev) * (1 << 18)).astype(np.int32)
+    centre = int(np.rint(0.5 * side))  # lidar_cloud maps the sensor, 0 m, to (0 + 125) / 250 of the grid
+    return np.array([centre, centre, centre], np.int32), thetas
+
+
 def random_cloud(n, seed=1, bits=6, c=3, bitdepth=8, dup_fraction=0.0):
     """Uniform random voxels in a small cube (dense occupancy -> every
     neighbour pattern occurs), optional exact duplicates."""

@@ -322,6 +322,48 @@ int gpcc_dev_attr_to_spherical(
   const void* d_xyz, void* d_pos_out, void* d_bbox);
 
 /* ------------------------------------------------------------------ */
+/* the reference frame of an inter-predicted LoD slice                  */
+
+/* What the reference does to the previous frame in front of the lifting and predicting coders of a slice with
+ * attribute inter prediction (encoder.cpp:1215-1236, decoder.cpp:926-947): the bounding box of the current
+ * slice's attribute-domain positions (computeBoundingBox), and of the WHOLE previous frame in that domain
+ * (_refFrameAlt, all slices appended) the points inside the box (Box3::contains, PCCMath.h:469-474, inclusive on
+ * all six faces), in order, with their attributes -- an ordered compaction; the order is part of the result.
+ * The cropped frame is what gpcc_lod_build_inter and the gpcc_*_attr_inter entries take as xyz_ref / attrs_ref.
+ *
+ * Domain: every coordinate of the frame and of the slices' boxes in [0, 2^21), as for the Morton sort.  A
+ * coordinate outside it makes the call fail with GPCC_ERR_INVALID_ARG (the context's sticky error word; the
+ * context works afterwards).
+ *
+ * Not covered, left to the caller: offsetAndScaleShift (for the LoD coders the reference overwrites the shifted
+ * cloud, encoder.cpp:1218) and bi-prediction's merge of two frames (an append). */
+
+/* Device tier.  offsets [num_slices + 1], d_xyz int32 [offsets[num_slices]][3]: the current slices;
+ * d_xyz_frame int32 [n_frame][3], d_attrs_frame int32 [n_frame][c], c in 1..3: the previous frame;
+ * d_xyz_ref int32 [capacity][3], d_attrs_ref int32 [capacity][c] out: the slices' cropped frames back to back,
+ * slice s at [ref_offsets[s], ref_offsets[s + 1]); ref_offsets host int64 [num_slices + 1] out;
+ * bbox host int32 [num_slices][6] out (min, max), may be NULL.
+ * The call waits ONCE on the context's stream, behind the count and its scan, and fills ref_offsets (and bbox) in
+ * every case that got that far; the scatter is enqueued and the call returns.  If ref_offsets[num_slices] >
+ * capacity: GPCC_ERR_INVALID_ARG and nothing is written to d_xyz_ref / d_attrs_ref, so that the caller can size
+ * the buffers and call again.  A slice may keep nothing (an empty segment: code it with the intra entry).
+ * The outputs must not alias the frame (an ordered compaction in place races across tiles): equal pointers give
+ * GPCC_ERR_INVALID_ARG.  Argument checks run ahead of the context. */
+int gpcc_dev_attr_ref_crop(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz, int32_t n_frame,
+  const void* d_xyz_frame, const void* d_attrs_frame, int32_t c, void* d_xyz_ref, void* d_attrs_ref,
+  int64_t capacity, int64_t* ref_offsets, int32_t* bbox);
+
+/* Host tier, one slice, synchronous: upload, the same kernels, download.  xyz [n][3] the current slice;
+ * xyz_ref [capacity][3], attrs_ref [capacity][c] out; *n_ref out: the number of points kept (written in every
+ * case that got as far as the count, also when it exceeds capacity: GPCC_ERR_INVALID_ARG then, and nothing else
+ * is written); bbox [6] out, may be NULL. */
+int gpcc_attr_ref_crop(
+  gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int32_t n_frame, const int32_t* xyz_frame,
+  const int32_t* attrs_frame, int32_t c, int32_t* xyz_ref, int32_t* attrs_ref, int32_t capacity, int32_t* n_ref,
+  int32_t* bbox);
+
+/* ------------------------------------------------------------------ */
 /* lifting transform (predictors given)                                 */
 
 #define GPCC_MAX_LODS 32
@@ -520,7 +562,10 @@ int gpcc_lod_build_inter(
  * behind the n working values and flagged neighbours point there); that
  * arrangement runs under the CPU emulator against the oracle
  * (tests/test_emu_lod.py) and the entry's first hardware run is
- * tests/test_zz_gpu_inter_lod.py in the round-end tier. */
+ * tests/test_zz_gpu_inter_lod.py in the round-end tier.
+ * A caller that has the slice's positions rather than the structure takes
+ * gpcc_lift_encode_attr_inter / gpcc_lift_decode_attr_inter below: build and
+ * transform in one call, the structure never leaves the device. */
 int gpcc_lift_forward_inter(
   gpcc_ctx* ctx, const gpcc_lift_params* params, int32_t n,
   const int32_t* neigh_count, const int32_t* neigh_index,
@@ -685,7 +730,9 @@ int gpcc_pred_inverse(
  * STATUS (round 3): the DAG pass in its inter build and the spare-entry
  * arrangement run under the CPU emulator against the oracle
  * (tests/test_emu_lod.py); first hardware run: tests/test_zz_gpu_inter_lod.py
- * in the round-end tier. */
+ * in the round-end tier.
+ * Build and transform in one call: gpcc_pred_encode_attr_inter /
+ * gpcc_pred_decode_attr_inter below. */
 int gpcc_pred_forward_inter(
   gpcc_ctx* ctx, const gpcc_pred_params* params, int32_t n,
   const int32_t* neigh_count, const int32_t* neigh_index,
@@ -697,6 +744,63 @@ int gpcc_pred_inverse_inter(
   const int32_t* neigh_weight, const int32_t* inter_ref, const int32_t* indexes,
   int32_t* attrs, const int32_t* attrs_ref, int32_t n_ref,
   const int32_t* values);
+
+/* ------------------------------------------------------------------ */
+/* a slice with attribute inter prediction in one call                  */
+/* gpcc_lod_build_inter followed by gpcc_lift_forward_inter / gpcc_pred_forward_inter (or the inverses) with the
+ * structure left on the device: what AttributeEncoder::encode / AttributeDecoder::decode do for a reflectance
+ * slice with enableAttrInterPred minus the entropy loop, for the lifting and the predicting transform.  The same
+ * kernels, the same results; the two-call path moves the structure (44 bytes per point) over PCIe twice.
+ *   lod         as gpcc_lod_build_inter takes it
+ *   lift / pred in: QP layers and tools; out: num_lods / num_points_in_lod, as gpcc_lift_encode_attr
+ *   xyz [n][3]; attrs [n] in: the source (encoder), out: the clipped reconstruction, point order
+ *   coeffs / values [n] out (encoder) or in (decoder), coding order; indexes [n] out, may be NULL
+ *   xyz_ref [n_ref][3], attrs_ref [n_ref], search_range, frame_distance as gpcc_lod_build_inter (the frame
+ *               cropped to the slice's box: gpcc_attr_ref_crop)
+ * One component by signature.  Checked ahead of the context: a null pointer, n <= 0, n_ref <= 0 or
+ * search_range < 0 give GPCC_ERR_INVALID_ARG; scalable lifting, canonical_point_order_flag, a chunked sort or QP
+ * regions give GPCC_ERR_UNSUPPORTED.  A declined call leaves the caller's buffers and parameter block untouched. */
+int gpcc_lift_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz, int32_t* attrs,
+  int32_t* coeffs, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, int32_t frame_distance);
+int gpcc_lift_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz, int32_t* attrs,
+  const int32_t* coeffs, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref,
+  int32_t n_ref, int32_t search_range, int32_t frame_distance);
+int gpcc_pred_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, const int32_t* xyz, int32_t* attrs,
+  int32_t* values, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, int32_t frame_distance);
+int gpcc_pred_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, const int32_t* xyz, int32_t* attrs,
+  const int32_t* values, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref,
+  int32_t n_ref, int32_t search_range, int32_t frame_distance);
+
+/* Device tier: a batch in HBM on the context's stream, as gpcc_dev_lift_encode_attr (c = 1, no side
+ * coefficients).  lift / pred [num_slices]; d_attrs in place; d_indexes may be NULL.  Slice s takes the frame
+ * segment [ref_offsets[s], ref_offsets[s + 1]) of d_xyz_ref int32 [..][3] / d_attrs_ref int32 [..]: exactly what
+ * gpcc_dev_attr_ref_crop leaves (ref_offsets host int64 [num_slices + 1]) -- the reference frame of slice t + 1
+ * is the reconstruction of frame t, which such a caller has in HBM; nothing of it passes through the host.
+ * An empty segment gives GPCC_ERR_INVALID_ARG before any work is enqueued (the reference asserts a non-empty
+ * frame: code such a slice with the intra entry).  A frame coordinate outside [0, 2^21) is found on the device:
+ * the call returns GPCC_ERR_INVALID_ARG and the context works afterwards.  Other refusals as the host tier's. */
+int gpcc_dev_lift_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, void* d_coeffs, void* d_indexes, const int64_t* ref_offsets,
+  const void* d_xyz_ref, const void* d_attrs_ref, int32_t search_range, int32_t frame_distance);
+int gpcc_dev_lift_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, const void* d_coeffs, void* d_indexes, const int64_t* ref_offsets,
+  const void* d_xyz_ref, const void* d_attrs_ref, int32_t search_range, int32_t frame_distance);
+int gpcc_dev_pred_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, void* d_values, void* d_indexes, const int64_t* ref_offsets,
+  const void* d_xyz_ref, const void* d_attrs_ref, int32_t search_range, int32_t frame_distance);
+int gpcc_dev_pred_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, const void* d_values, void* d_indexes, const int64_t* ref_offsets,
+  const void* d_xyz_ref, const void* d_attrs_ref, int32_t search_range, int32_t frame_distance);
 
 /* ------------------------------------------------------------------ */
 /* slice-level inter / intra decision (attrInterIntraSliceRDO)          */

@@ -34,6 +34,10 @@ ABI_SYMBOLS = [
     "gpcc_dev_lift_decode_attr_partial",
     "gpcc_lift_encode_attr_rdo", "gpcc_pred_encode_attr_rdo", "gpcc_slice_rdo_choose",
     "gpcc_attr_to_spherical", "gpcc_dev_attr_to_spherical",
+    "gpcc_attr_ref_crop", "gpcc_dev_attr_ref_crop",
+    "gpcc_lift_encode_attr_inter", "gpcc_lift_decode_attr_inter", "gpcc_pred_encode_attr_inter",
+    "gpcc_pred_decode_attr_inter", "gpcc_dev_lift_encode_attr_inter", "gpcc_dev_lift_decode_attr_inter",
+    "gpcc_dev_pred_encode_attr_inter", "gpcc_dev_pred_decode_attr_inter",
     "gpcc_ctx_reserve",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_guard_selftest",
@@ -153,6 +157,16 @@ def load():
     # attribute positions in the pseudo-spherical domain (spherical_coord_flag)
     lib.gpcc_attr_to_spherical.argtypes = [vp, C.POINTER(SphericalParams), vp, i32, vp, vp]
     lib.gpcc_dev_attr_to_spherical.argtypes = [vp, C.POINTER(SphericalParams), i32, i64p, vp, vp, vp]
+    # the reference frame of an inter-predicted LoD slice: the previous frame cropped to the slices' boxes
+    lib.gpcc_dev_attr_ref_crop.argtypes = [vp, i32, i64p, vp, i32, vp, vp, i32, vp, vp, C.c_int64, i64p, vp]
+    lib.gpcc_attr_ref_crop.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(i32), vp]
+    # a slice with attribute inter prediction in one call, and the device tier's batches
+    for name, params in (("lift", LiftParams), ("pred", PredParams)):
+        for op in ("encode", "decode"):
+            getattr(lib, f"gpcc_{name}_{op}_attr_inter").argtypes = [
+                vp, C.POINTER(LodParams), C.POINTER(params), vp, vp, vp, vp, i32, vp, vp, i32, i32, i32]
+            getattr(lib, f"gpcc_dev_{name}_{op}_attr_inter").argtypes = [
+                vp, C.POINTER(LodParams), vp, i32, i64p, vp, vp, vp, vp, i64p, vp, vp, i32, i32]
     lib.gpcc_multi_create.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
     lib.gpcc_multi_destroy.argtypes = [vp]
     lib.gpcc_multi_destroy.restype = None

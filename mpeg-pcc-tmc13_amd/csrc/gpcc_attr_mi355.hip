@@ -53,6 +53,7 @@
 #include "recolour_kernels.hpp"
 #include "slice_rdo.hpp"
 #include "spherical.hpp"
+#include "ref_crop.hpp"
 
 using namespace gpcc;
 
@@ -1321,6 +1322,11 @@ check_device_error(gpcc_ctx* ctx)
         GPCC_ERR_INVALID_ARG,
         "spherical attribute positions: a point outside the domain (a coordinate 2^22 or more away from the laser "
         "origin, or a scaled coordinate outside [0, 2^21)); the result is invalid");
+    if (code == kRefCropErrorRange)
+      return fail(
+        GPCC_ERR_INVALID_ARG,
+        "reference frame crop: a coordinate of the frame or of a slice's bounding box outside [0, 2^21); the result "
+        "is invalid");
     if (code == 2)
       return fail(
         GPCC_ERR_INVALID_ARG,
@@ -1844,8 +1850,9 @@ check_partial(const PartialDecode& pd, int64_t n, bool scalable, int attr_encodi
 
 // Attribute inter prediction (n_frame > 0): the working arrays get n_frame entries
 // BEHIND the n predictors.  a[n + r] holds the reference frame's attribute r in fixed
-// point (h_frame, host memory, [n_frame][C]) and the caller has pointed every neighbour
-// that lives in that frame at n + r: PCCLiftPredict then reads the frame's value
+// point (h_frame, host memory, [n_frame][C]; or d_frame_attrs, the frame's int32 attributes
+// already on the device, which frame_stage_lift_kernel shifts into place) and the caller has
+// pointed every neighbour that lives in that frame at n + r: PCCLiftPredict then reads the frame's value
 // (PCCTMC3Common.h:735-740) and what PCCLiftUpdate / PCCComputeQuantizationWeights skip for
 // such a neighbour (:799-800, :845-846) lands in entries nobody reads -- the kernels are
 // the intra ones, untouched.
@@ -1854,7 +1861,8 @@ int
 launch_lift(
   gpcc_ctx* ctx, bool encoder, const gpcc_lift_params* p, int n,
   const LodCoderDev& d, int8_t* d_lcp_io, char* scratch, int n_frame = 0,
-  const int64_t* h_frame = nullptr, const PartialDecode* partial = nullptr)
+  const int64_t* h_frame = nullptr, const PartialDecode* partial = nullptr,
+  const int32_t* d_frame_attrs = nullptr)
 {
   hipStream_t st = ctx->stream;
   LiftCtx cx{};
@@ -1926,7 +1934,11 @@ launch_lift(
   cx.up = ar.take<unsigned long long>(n_ext * C);
   cx.lcp_sums = ar.take<long long>(2 * GPCC_MAX_LODS);
   cx.rsqrt = &ctx->d_lut->rsqrt;
-  if (n_frame > 0)
+  if (n_frame > 0 && d_frame_attrs) {
+    Timer t(ctx, "frame_stage_lift");
+    frame_stage_lift_kernel<<<grid_for((int64_t)n_frame * C, 256), 256, 0, st>>>(
+      d_frame_attrs, (int64_t)n_frame * C, cx.a + (size_t)n * C);
+  } else if (n_frame > 0)
     HIP_TRY(h2d_user(ctx, cx.a + (size_t)n * C, h_frame, sizeof(int64_t) * (size_t)n_frame * C, st));
 
   const int* npl = cx.npl;
@@ -2077,8 +2089,8 @@ launch_pred(
   int8_t* d_icp, char* scratch,
   // attribute inter prediction (n_frame > 0, one component): h_frame [n_frame] the reference
   // frame's reflectances (host memory); the caller has pointed the neighbours that live in
-  // that frame at n + r (PredCtx::frame_attr)
-  int n_frame = 0, const int32_t* h_frame = nullptr)
+  // that frame at n + r (PredCtx::frame_attr); d_frame_attrs: the same values already on the device
+  int n_frame = 0, const int32_t* h_frame = nullptr, const int32_t* d_frame_attrs = nullptr)
 {
   hipStream_t st = ctx->stream;
   PredCtx cx{};
@@ -2134,7 +2146,10 @@ launch_pred(
   long long* scan_sums = ar.take<long long>((size_t)n / kKdScanBlock + 2);
   int32_t* d_frame = ar.take<int32_t>((size_t)n_frame + 1);
   if (n_frame > 0) {
-    HIP_TRY(h2d_user(ctx, d_frame, h_frame, sizeof(int32_t) * (size_t)n_frame, st));
+    if (d_frame_attrs)
+      HIP_TRY(hipMemcpyAsync(d_frame, d_frame_attrs, sizeof(int32_t) * (size_t)n_frame, hipMemcpyDeviceToDevice, st));
+    else
+      HIP_TRY(h2d_user(ctx, d_frame, h_frame, sizeof(int32_t) * (size_t)n_frame, st));
     cx.frame_attr = d_frame;
   }
   // the DAG pass: its inter-prediction build where neighbours may live in the reference frame
@@ -2302,9 +2317,16 @@ pred_check_error(gpcc_ctx* ctx)
 // Everything the drivers below need to know about a coder: its parameter block, limits, the side block
 // (last-component / inter-component coefficients), scratch, launch sequence and closing error check.
 
+// the reference frame's attributes [n_frame] as a launcher takes them, and where they live
+struct CoderFrame {
+  std::vector<int64_t> fixed;      // host, lifting: in fixed point (<< kFixedPointAttributeShift)
+  const int32_t* host = nullptr;   // host, predicting: the caller's reflectances as they are
+  const int32_t* dev = nullptr;    // on the device already (either coder); the host members are unused then
+};
+
 struct LiftCoder {
   using Params = gpcc_lift_params;
-  using Frame = std::vector<int64_t>;  // the reference frame as the launcher takes it: fixed point
+  using Frame = CoderFrame;
   static constexpr int32_t kMaxN = kMaxPoints;
   static constexpr size_t kSideBytes = GPCC_MAX_LODS;
   static constexpr const char* kBadCount = "null buffer or attribute count not 1..3";
@@ -2317,9 +2339,10 @@ struct LiftCoder {
   static size_t scratch_bytes(int n, int c, int n_frame) { return lift_scratch_bytes(n + n_frame, c); }
   static Frame stage_frame(const int32_t* attrs_ref, size_t count)
   {
-    Frame f(count);
+    Frame f;
+    f.fixed.resize(count);
     for (size_t t = 0; t < count; t++)
-      f[t] = (int64_t)attrs_ref[t] * 256;  // << kFixedPointAttributeShift
+      f.fixed[t] = (int64_t)attrs_ref[t] * 256;  // << kFixedPointAttributeShift
     return f;
   }
   static int launch(
@@ -2327,7 +2350,7 @@ struct LiftCoder {
     int n_frame, const Frame& frame, const PartialDecode* partial)
   {
     switch (c) {
-    case 1: return launch_lift<1>(ctx, encoder, p, n, d, d_side, scratch, n_frame, frame.data(), partial);
+    case 1: return launch_lift<1>(ctx, encoder, p, n, d, d_side, scratch, n_frame, frame.fixed.data(), partial, frame.dev);
     case 2: return launch_lift<2>(ctx, encoder, p, n, d, d_side, scratch, 0, nullptr, partial);
     default: return launch_lift<3>(ctx, encoder, p, n, d, d_side, scratch, 0, nullptr, partial);
     }
@@ -2337,7 +2360,7 @@ struct LiftCoder {
 
 struct PredCoder {
   using Params = gpcc_pred_params;
-  using Frame = const int32_t*;  // the caller's reflectances as they are
+  using Frame = CoderFrame;
   static constexpr int32_t kMaxN = 1 << 27;
   static constexpr size_t kSideBytes = GPCC_MAX_LODS * 3;
   static constexpr const char* kBadCount = "null buffer or attribute count not 1 / 3";
@@ -2348,13 +2371,18 @@ struct PredCoder {
   static bool side_on(const Params& p, int c) { return c == 3 && p.inter_component_prediction_enabled_flag; }
   static int check(const Params* p, int n, int c, bool encoder) { return check_pred_params(p, n, c, encoder); }
   static size_t scratch_bytes(int n, int, int n_frame) { return pred_scratch_bytes(n, n_frame); }
-  static Frame stage_frame(const int32_t* attrs_ref, size_t) { return attrs_ref; }
+  static Frame stage_frame(const int32_t* attrs_ref, size_t)
+  {
+    Frame f;
+    f.host = attrs_ref;
+    return f;
+  }
   // (no partial decode of the predicting transform: check_partial refuses it)
   static int launch(
     gpcc_ctx* ctx, bool encoder, const Params* p, int n, int c, const LodCoderDev& d, int8_t* d_side, char* scratch,
     int n_frame, const Frame& frame, const PartialDecode*)
   {
-    return c == 1 ? launch_pred<1>(ctx, encoder, p, n, d, d_side, scratch, n_frame, frame)
+    return c == 1 ? launch_pred<1>(ctx, encoder, p, n, d, d_side, scratch, n_frame, frame.host, frame.dev)
                   : launch_pred<3>(ctx, encoder, p, n, d, d_side, scratch);
   }
   static int finish(gpcc_ctx* ctx) { return pred_check_error(ctx); }
@@ -3212,12 +3240,13 @@ struct LodDeviceOut {
   size_t arena_end = 0;            // first free byte behind the build's workspace
 };
 
-// the reference frame of attribute inter prediction (host memory, point order)
+// the reference frame of attribute inter prediction (point order)
 struct LodInterFrame {
   const int32_t* xyz;
   int32_t n;
   int32_t search_range;    // abh.attrInterPredSearchRange: replaces both LoD search ranges
   int32_t frame_distance;  // AttributeInterPredParams::frameDistance
+  bool on_device = false;  // xyz is a device pointer: not inspected on the host (as xyz_on_device)
 };
 
 // -> the per-point offsets in `where` (device, [n][2]), or null when the block names no region
@@ -3269,13 +3298,15 @@ lod_build_core(
       return rp;
   }
   if (frame) {
-    if (!frame->xyz || frame->n <= 0 || frame->n > kMaxPoints || frame->search_range < 0 || xyz_on_device)
+    // (positions on the device and a frame in host memory: no entry hands that over)
+    if (!frame->xyz || frame->n <= 0 || frame->n > kMaxPoints || frame->search_range < 0
+        || (xyz_on_device && !frame->on_device))
       return fail(GPCC_ERR_INVALID_ARG, "reference frame: null, empty, too large or a negative search range");
     if (lp->scalable_lifting_enabled_flag || lp->canonical_point_order_flag || lp->max_points_per_sort_log2_plus1)
       return fail(
         GPCC_ERR_UNSUPPORTED,
         "inter prediction together with scalable lifting / canonical point order stays on the reference CPU path");
-    for (int64_t i = 0; i < (int64_t)frame->n * 3; i++)
+    for (int64_t i = 0; !frame->on_device && i < (int64_t)frame->n * 3; i++)
       if (frame->xyz[i] < 0 || frame->xyz[i] >= (1 << 21))
         return fail(GPCC_ERR_INVALID_ARG, "reference frame coordinate outside [0, 2^21)");
   }
@@ -3425,12 +3456,20 @@ lod_build_core(
     // computeNearestNeighbors :1270-1292) -- the same at every level of detail
     int32_t* fbox[3][2] = {};
     if (frame) {
-      HIP_TRY(h2d_user(ctx, d_fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, st));
-      int32_t fmx = 0;
-      for (size_t i = 0; i < 3 * NF; i++)
-        fmx = std::max(fmx, frame->xyz[i]);
       const int saved = ctx->morton_bits;
-      ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)fmx));
+      if (frame->on_device) {
+        // the range check is the sticky error word's; the Morton-bits hint bounds the sort's passes as it does for
+        // the slice's own positions
+        HIP_TRY(hipMemcpyAsync(d_fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, hipMemcpyDeviceToDevice, st));
+        Timer tm(ctx, "ref_frame_range");
+        ref_frame_range_kernel<<<grid_for((int64_t)(3 * NF), 256), 256, 0, st>>>(d_fxyz, (int64_t)(3 * NF), ctx->d_error);
+      } else {
+        HIP_TRY(h2d_user(ctx, d_fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, st));
+        int32_t fmx = 0;
+        for (size_t i = 0; i < 3 * NF; i++)
+          fmx = std::max(fmx, frame->xyz[i]);
+        ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)fmx));
+      }
       const int64_t offs[2] = {0, (int64_t)NF};
       int r = dev_morton_sort(ctx, 1, offs, d_fxyz, d_fcode, d_forder);
       ctx->morton_bits = saved;
@@ -3985,6 +4024,16 @@ check_rdo_args(
   return GPCC_OK;
 }
 
+// the neighbours the build flagged as living in the frame, moved behind the n predictors (launch_lift / launch_pred)
+void
+frame_neighbours_on_device(gpcc_ctx* ctx, int n, const LodDeviceOut& o, int32_t* ni)
+{
+  Timer tm(ctx, "rdo_frame_neighbours");
+  hipLaunchKernelGGL(
+    rdo_frame_neighbours_kernel, dim3(grid_for((int64_t)n * 3, 256)), dim3(256), 0, ctx->stream, n, o.count, o.inter_ref,
+    o.neigh_index, ni);
+}
+
 template<class Coder>
 int
 rdo_attr_driver(
@@ -4030,10 +4079,7 @@ rdo_attr_driver(
       ctx, true, false, &p, n, 1, o, what, nf, frame, nullptr,
       [&](const SliceBlocks& b, LodCoderDev& d) -> int {
         if (inter) {
-          Timer tm(ctx, "rdo_frame_neighbours");
-          hipLaunchKernelGGL(
-            rdo_frame_neighbours_kernel, dim3(grid_for((int64_t)N * 3, 256)), dim3(256), 0, st, n, o.count,
-            o.inter_ref, o.neigh_index, b.ni);
+          frame_neighbours_on_device(ctx, n, o, b.ni);
           d.ni = b.ni;
         }
         HIP_TRY(hipMemcpyAsync(d_rec[k], d_orig, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
@@ -4084,6 +4130,85 @@ rdo_attr_driver(
   int r = run();
   cleanup();
   return r;
+}
+
+// ---- a slice with attribute inter prediction in one call -------------------------------------------
+// Candidate 0 of rdo_attr_driver on its own, for the encoder and the decoder: the structure built over the slice
+// and its reference frame never leaves the device (gpcc_lod_build_inter + gpcc_*_forward_inter download it and
+// upload it again: 88 bytes per point over PCIe).
+
+// what can be refused without a context (so: on every machine); one component by signature
+template<class Params>
+int
+check_inter_args(const gpcc_lod_params* lod, const Params* params, int32_t num_params, int32_t search_range)
+{
+  if (!lod || !params)
+    return fail(GPCC_ERR_INVALID_ARG, "null parameter block");
+  if (search_range < 0)
+    return fail(GPCC_ERR_INVALID_ARG, "a negative search range");
+  if (lod->scalable_lifting_enabled_flag)
+    return fail(
+      GPCC_ERR_UNSUPPORTED, "inter prediction together with scalable lifting stays on the reference CPU path");
+  if (lod->canonical_point_order_flag || lod->max_points_per_sort_log2_plus1)
+    return fail(
+      GPCC_ERR_UNSUPPORTED,
+      "inter prediction together with canonical point order / a chunked sort stays on the reference CPU path");
+  for (int s = 0; s < num_params; s++)
+    if (params[s].num_qp_regions != 0)
+      return fail(GPCC_ERR_UNSUPPORTED, "inter prediction together with QP regions stays on the reference CPU path");
+  return GPCC_OK;
+}
+
+template<class Coder>
+int
+inter_attr_driver(
+  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, typename Coder::Params* params, const int32_t* xyz,
+  int32_t* attrs, int32_t* values, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref,
+  int32_t n_ref, int32_t search_range, int32_t frame_distance)
+{
+  if (!xyz || !attrs || !values || !xyz_ref || !attrs_ref)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  if (n <= 0 || n_ref <= 0)
+    return fail(GPCC_ERR_INVALID_ARG, "n <= 0 or n_ref <= 0");
+  int r = check_inter_args(lod, params, 1, search_range);
+  if (r)
+    return r;
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  if (n > Coder::kMaxN || n_ref > Coder::kMaxN)
+    return fail(GPCC_ERR_INVALID_ARG, "too many points per call");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const unsigned what = kBlkFrameNi | kBlkAttrs | kBlkValues;
+  const typename Coder::Frame frame = Coder::stage_frame(attrs_ref, (size_t)n_ref);
+  LodInterFrame lod_frame{xyz_ref, n_ref, search_range, frame_distance};
+  LodDeviceOut o;
+  r = lod_build_core(ctx, lod, xyz, n, slice_reserve<Coder>(n, 1, n_ref, what), &o, false, &lod_frame);
+  if (r)
+    return r;
+  const size_t bytes = sizeof(int32_t) * (size_t)n;
+  typename Coder::Params p = *params;  // (the caller's block is written when the call has succeeded)
+  r = code_slice<Coder>(
+    ctx, encoder, false, &p, n, 1, o, what, n_ref, frame, nullptr,
+    [&](const SliceBlocks& b, LodCoderDev& d) -> int {
+      frame_neighbours_on_device(ctx, n, o, b.ni);
+      d.ni = b.ni;
+      HIP_TRY(h2d_user(ctx, encoder ? b.attrs : b.values, encoder ? attrs : values, bytes, st));
+      return GPCC_OK;
+    },
+    [&](const SliceBlocks& b) -> int {
+      HIP_TRY(d2h_user(ctx, attrs, b.attrs, bytes, st));
+      if (encoder)
+        HIP_TRY(d2h_user(ctx, values, b.values, bytes, st));
+      if (indexes)
+        HIP_TRY(d2h_user(ctx, indexes, o.indexes, bytes, st));
+      return GPCC_OK;
+    });
+  if (r)
+    return r;
+  params->num_lods = p.num_lods;
+  memcpy(params->num_points_in_lod, p.num_points_in_lod, sizeof(p.num_points_in_lod));
+  return GPCC_OK;
 }
 
 int
@@ -4804,6 +4929,60 @@ gpcc_lod_build_inter(
 }
 
 int
+gpcc_lift_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz, int32_t* attrs,
+  int32_t* coeffs, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    inter_attr_driver<LiftCoder>(
+      ctx, true, lod, lift, xyz, attrs, coeffs, indexes, n, xyz_ref, attrs_ref, n_ref, search_range, frame_distance),
+    n);
+}
+
+int
+gpcc_lift_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz, int32_t* attrs,
+  const int32_t* coeffs, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    inter_attr_driver<LiftCoder>(
+      ctx, false, lod, lift, xyz, attrs, const_cast<int32_t*>(coeffs), indexes, n, xyz_ref, attrs_ref, n_ref,
+      search_range, frame_distance),
+    n);
+}
+
+int
+gpcc_pred_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, const int32_t* xyz, int32_t* attrs,
+  int32_t* values, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    inter_attr_driver<PredCoder>(
+      ctx, true, lod, pred, xyz, attrs, values, indexes, n, xyz_ref, attrs_ref, n_ref, search_range, frame_distance),
+    n);
+}
+
+int
+gpcc_pred_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, const int32_t* xyz, int32_t* attrs,
+  const int32_t* values, int32_t* indexes, int32_t n, const int32_t* xyz_ref, const int32_t* attrs_ref, int32_t n_ref,
+  int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    inter_attr_driver<PredCoder>(
+      ctx, false, lod, pred, xyz, attrs, const_cast<int32_t*>(values), indexes, n, xyz_ref, attrs_ref, n_ref,
+      search_range, frame_distance),
+    n);
+}
+
+int
 gpcc_lift_encode_attr(
   gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, const int32_t* xyz,
   int32_t* attrs, int32_t* coeffs, int8_t* lcp_coeffs, int32_t* indexes, int32_t n, int32_t c)
@@ -5096,6 +5275,231 @@ gpcc_dev_attr_to_spherical(
 
 }  // extern "C"
 
+// ---- the reference frame of an inter-predicted LoD slice (ref_crop.hpp) ------------------------
+namespace {
+
+// what can be refused without a context; the outputs may be null with capacity 0 (a call that only sizes)
+int
+check_ref_crop_args(
+  int64_t n_frame, const void* xyz_frame, const void* attrs_frame, int32_t c, const void* xyz_ref,
+  const void* attrs_ref, int64_t capacity)
+{
+  if (!xyz_frame || !attrs_frame)
+    return fail(GPCC_ERR_INVALID_ARG, "null frame buffer");
+  if (n_frame <= 0 || n_frame > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "n_frame <= 0 or more than 2^29 frame points");
+  if (c < 1 || c > 3)
+    return fail(GPCC_ERR_INVALID_ARG, "attribute count not in 1..3");
+  if (capacity < 0 || (capacity > 0 && (!xyz_ref || !attrs_ref)))
+    return fail(GPCC_ERR_INVALID_ARG, "negative capacity or null output buffer");
+  if ((xyz_ref && xyz_ref == xyz_frame) || (attrs_ref && attrs_ref == attrs_frame))
+    return fail(GPCC_ERR_INVALID_ARG, "the cropped frame must not alias the frame: an ordered compaction in place races");
+  return GPCC_OK;
+}
+
+// One wait on the stream, behind the count and its scan; the scatter is enqueued behind it.  ref_offsets and
+// bbox (host) are filled as soon as they are known.
+int
+dev_ref_crop(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz, int32_t n_frame,
+  const void* d_xyz_frame, const void* d_attrs_frame, int32_t c, void* d_xyz_ref, void* d_attrs_ref, int64_t capacity,
+  int64_t* ref_offsets, int32_t* bbox)
+{
+  if (!d_xyz || !ref_offsets)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  if (num_slices < 1 || !offsets || offsets[0] != 0)
+    return fail(GPCC_ERR_INVALID_ARG, "bad slice offsets");
+  for (int i = 0; i < num_slices; i++)
+    if (offsets[i + 1] <= offsets[i])
+      return fail(GPCC_ERR_INVALID_ARG, "empty or unordered slice");
+  if (offsets[num_slices] > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per batch");
+  int r = check_ref_crop_args(n_frame, d_xyz_frame, d_attrs_frame, c, d_xyz_ref, d_attrs_ref, capacity);
+  if (r)
+    return r;
+  // (every slice may keep the whole frame: the scanned counts are int32)
+  if ((int64_t)num_slices * ref_crop_tiles(n_frame) > kRefCropMaxPairs || (int64_t)num_slices * n_frame > INT32_MAX)
+    return fail(GPCC_ERR_INVALID_ARG, "too many slices for a frame of this size in one call");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  // the current slices' tiles never straddle a slice (spherical.hpp RplArgs)
+  std::vector<int32_t> meta(2 * ((size_t)num_slices + 1));
+  int32_t* h_pt = meta.data();
+  int32_t* h_tile = meta.data() + num_slices + 1;
+  h_tile[0] = 0;
+  for (int s = 0; s <= num_slices; s++)
+    h_pt[s] = (int32_t)offsets[s];
+  for (int s = 0; s < num_slices; s++)
+    h_tile[s + 1] = h_tile[s] + rpl_tiles(offsets[s + 1] - offsets[s]);
+
+  const size_t ncount = ref_crop_count_entries(num_slices, n_frame), nsum = ref_crop_sum_entries(num_slices, n_frame);
+  Arena measure;
+  measure.take<int32_t>(meta.size());
+  measure.take<int32_t>(6 * (size_t)num_slices);
+  measure.take<int32_t>(ncount);
+  measure.take<long long>(nsum);
+  measure.take<int32_t>((size_t)num_slices + 1);
+  r = ensure_arena(ctx, measure.used);
+  if (r)
+    return r;
+  Arena& ar = ctx->arena;
+  ar.reset();
+  int32_t* d_meta = ar.take<int32_t>(meta.size());
+  int32_t* d_box = ar.take<int32_t>(6 * (size_t)num_slices);
+  int32_t* d_counts = ar.take<int32_t>(ncount);
+  long long* d_sums = ar.take<long long>(nsum);
+  int32_t* d_off = ar.take<int32_t>((size_t)num_slices + 1);
+  HIP_TRY(h2d_user(ctx, d_meta, meta.data(), meta.size() * sizeof(int32_t), st));
+
+  RplArgs sl{};
+  sl.src = (const int32_t*)d_xyz;
+  sl.pt_off = d_meta;
+  sl.tile_off = d_meta + num_slices + 1;
+  sl.num_slices = num_slices;
+  sl.num_tiles = h_tile[num_slices];
+  RefCropArgs a{};
+  a.xyz_frame = (const int32_t*)d_xyz_frame;
+  a.attrs_frame = (const int32_t*)d_attrs_frame;
+  a.bbox = d_box;
+  a.counts = d_counts;
+  a.offsets = d_off;
+  a.xyz_ref = (int32_t*)d_xyz_ref;
+  a.attrs_ref = (int32_t*)d_attrs_ref;
+  a.error = ctx->d_error;
+  a.n_frame = n_frame;
+  a.c = c;
+  a.num_slices = num_slices;
+  a.num_tiles = ref_crop_tiles(n_frame);
+  auto span = [&](const char* name) { return Timer(ctx, name); };
+  HIP_TRY(ref_crop_count_launch(st, sl, a, d_sums, span));
+
+  // the one host wait: the offsets (and the boxes) through pinned memory
+  const size_t words = (size_t)num_slices + 1 + 6 * (size_t)num_slices;
+  HIP_TRY(small_reset(ctx));
+  int32_t* big = nullptr;
+  int32_t* h = (int32_t*)small_slot(ctx, words * sizeof(int32_t));
+  if (!h) {
+    HIP_TRY(hipHostMalloc((void**)&big, words * sizeof(int32_t)));
+    h = big;
+  }
+  auto wait = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(h, d_off, ((size_t)num_slices + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h + num_slices + 1, d_box, 6 * (size_t)num_slices * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (ctx->h_error)
+      HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s <= num_slices; s++)
+      ref_offsets[s] = h[s];
+    if (bbox)
+      memcpy(bbox, h + num_slices + 1, 6 * (size_t)num_slices * sizeof(int32_t));
+    return GPCC_OK;
+  };
+  r = wait();
+  if (big)
+    hipHostFree(big);
+  if (r)
+    return r;
+  r = check_device_error(ctx);
+  if (r)
+    return r;
+  if (ref_offsets[num_slices] > capacity)
+    return fail(
+      GPCC_ERR_INVALID_ARG, "the cropped frames need " + std::to_string(ref_offsets[num_slices])
+        + " points, capacity is " + std::to_string(capacity) + "; nothing was written");
+  if (ref_offsets[num_slices] > 0)
+    HIP_TRY(ref_crop_scatter_launch(st, a, span));
+  return GPCC_OK;
+}
+
+// synchronous; xyz_ref / attrs_ref are written only when the whole call has succeeded
+int
+host_ref_crop(
+  gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int32_t n_frame, const int32_t* xyz_frame, const int32_t* attrs_frame,
+  int32_t c, int32_t* xyz_ref, int32_t* attrs_ref, int32_t capacity, int32_t* n_ref, int32_t* bbox)
+{
+  if (!xyz || !n_ref || n <= 0)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer or n <= 0");
+  if (n > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per call");
+  int r = check_ref_crop_args(n_frame, xyz_frame, attrs_frame, c, xyz_ref, attrs_ref, capacity);
+  if (r)
+    return r;
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t N = (size_t)n, NF = (size_t)n_frame, cap = std::min((size_t)capacity, NF);
+  int32_t *d_xyz = nullptr, *d_fx = nullptr, *d_fa = nullptr, *d_ox = nullptr, *d_oa = nullptr;
+  auto run = [&]() -> int {
+    HIP_TRY(pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * N));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_fx, sizeof(int32_t) * 3 * NF));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_fa, sizeof(int32_t) * c * NF));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_ox, sizeof(int32_t) * 3 * std::max<size_t>(cap, 1)));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_oa, sizeof(int32_t) * c * std::max<size_t>(cap, 1)));
+    HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
+    HIP_TRY(h2d_user(ctx, d_fx, xyz_frame, sizeof(int32_t) * 3 * NF, st));
+    HIP_TRY(h2d_user(ctx, d_fa, attrs_frame, sizeof(int32_t) * c * NF, st));
+    const int64_t offs[2] = {0, n};
+    int64_t ro[2] = {0, -1};
+    int32_t box[6];
+    // (a crop never keeps more than the frame has: a larger capacity needs no larger buffer)
+    int r = dev_ref_crop(ctx, 1, offs, d_xyz, n_frame, d_fx, d_fa, c, d_ox, d_oa, (int64_t)cap, ro, box);
+    if (ro[1] >= 0)
+      *n_ref = (int32_t)ro[1];
+    if (r)
+      return r;
+    const size_t kept = (size_t)ro[1];
+    if (kept) {
+      HIP_TRY(d2h_user(ctx, xyz_ref, d_ox, sizeof(int32_t) * 3 * kept, st));
+      HIP_TRY(d2h_user(ctx, attrs_ref, d_oa, sizeof(int32_t) * c * kept, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bbox)
+      memcpy(bbox, box, sizeof(box));
+    return GPCC_OK;
+  };
+  r = run();
+  pool_free(ctx, d_oa);
+  pool_free(ctx, d_ox);
+  pool_free(ctx, d_fa);
+  pool_free(ctx, d_fx);
+  pool_free(ctx, d_xyz);
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int
+gpcc_dev_attr_ref_crop(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz, int32_t n_frame,
+  const void* d_xyz_frame, const void* d_attrs_frame, int32_t c, void* d_xyz_ref, void* d_attrs_ref, int64_t capacity,
+  int64_t* ref_offsets, int32_t* bbox)
+{
+  return counted(
+    ctx,
+    dev_ref_crop(
+      ctx, num_slices, offsets, d_xyz, n_frame, d_xyz_frame, d_attrs_frame, c, d_xyz_ref, d_attrs_ref, capacity,
+      ref_offsets, bbox),
+    n_frame);
+}
+
+int
+gpcc_attr_ref_crop(
+  gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int32_t n_frame, const int32_t* xyz_frame, const int32_t* attrs_frame,
+  int32_t c, int32_t* xyz_ref, int32_t* attrs_ref, int32_t capacity, int32_t* n_ref, int32_t* bbox)
+{
+  return counted(
+    ctx, host_ref_crop(ctx, xyz, n, n_frame, xyz_frame, attrs_frame, c, xyz_ref, attrs_ref, capacity, n_ref, bbox),
+    n_frame);
+}
+
+}  // extern "C"
+
 // ---- device tier of the LoD build and the lifting coder -----------------------------
 // Slices back to back in HBM, results left in HBM, workspace from the context's
 // arena: no allocation, no PCIe traffic but the few integers per level of detail
@@ -5304,6 +5708,75 @@ dev_lod_coder_attr(
   });
 }
 
+// ... and with attribute inter prediction (one component): slice s against the frame segment
+// [ref_offsets[s], ref_offsets[s + 1]) of d_xyz_ref / d_attrs_ref, which is what gpcc_dev_attr_ref_crop leaves.
+// Nothing of the frame passes through the host; a frame coordinate outside [0, 2^21) is the lane's sticky error
+// word, read when the slice has been coded.
+template<class Coder>
+int
+dev_inter_coder_attr(
+  gpcc_ctx* ctx, bool encoder, const gpcc_lod_params* lod, typename Coder::Params* params, int32_t num_slices,
+  const int64_t* offsets, const int32_t* d_xyz, int32_t* d_attrs, int32_t* d_values, int32_t* d_indexes,
+  const int64_t* ref_offsets, const int32_t* d_xyz_ref, const int32_t* d_attrs_ref, int32_t search_range,
+  int32_t frame_distance)
+{
+  if (!d_xyz || !d_attrs || !d_values || !ref_offsets || !d_xyz_ref || !d_attrs_ref)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  if (num_slices < 1 || !offsets || offsets[0] != 0)
+    return fail(GPCC_ERR_INVALID_ARG, "bad slice offsets");
+  int r = check_inter_args(lod, params, num_slices, search_range);
+  if (r)
+    return r;
+  if (ref_offsets[0] < 0)
+    return fail(GPCC_ERR_INVALID_ARG, "bad reference frame offsets");
+  for (int s = 0; s < num_slices; s++) {
+    // (the reference asserts a non-empty frame: such a slice is coded with the intra entry)
+    if (ref_offsets[s + 1] <= ref_offsets[s])
+      return fail(GPCC_ERR_INVALID_ARG, "empty or unordered reference frame segment");
+    if (ref_offsets[s + 1] - ref_offsets[s] > Coder::kMaxN || offsets[s + 1] - offsets[s] > Coder::kMaxN)
+      return fail(GPCC_ERR_INVALID_ARG, "too many points per slice");
+  }
+  r = check_slices(ctx, num_slices, offsets);
+  if (r)
+    return r;
+  return run_slices(ctx, num_slices, [&](gpcc_ctx* lane, int s) -> int {
+    hipStream_t st = lane->stream;
+    const size_t first = (size_t)offsets[s], N = (size_t)(offsets[s + 1] - offsets[s]);
+    const size_t ffirst = (size_t)ref_offsets[s];
+    const int32_t n = (int32_t)N, nf = (int32_t)(ref_offsets[s + 1] - ref_offsets[s]);
+    LodInterFrame lod_frame{d_xyz_ref + 3 * ffirst, nf, search_range, frame_distance, true};
+    LodDeviceOut o;
+    int r = lod_build_core(
+      lane, lod, d_xyz + 3 * first, n, slice_reserve<Coder>(n, 1, nf, kBlkFrameNi), &o, true, &lod_frame);
+    if (r)
+      return r;
+    typename Coder::Frame frame;
+    frame.dev = d_attrs_ref + ffirst;
+    r = code_slice<Coder>(
+      lane, encoder, false, params + s, n, 1, o, kBlkFrameNi, nf, frame, nullptr,
+      [&](const SliceBlocks& b, LodCoderDev& d) -> int {
+        frame_neighbours_on_device(lane, n, o, b.ni);
+        d.ni = b.ni;
+        d.attrs = d_attrs + first;
+        d.values = d_values + first;
+        return GPCC_OK;
+      },
+      [&](const SliceBlocks&) -> int {
+        if (d_indexes)
+          HIP_TRY(hipMemcpyAsync(d_indexes + first, o.indexes, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
+        return GPCC_OK;
+      });
+    if (r)
+      return r;
+    // the frame's range check (behind the coder's own use of the pinned word: launch_pred / pred_check_error)
+    if (lane->h_error) {
+      HIP_TRY(hipMemcpyAsync(lane->h_error, lane->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    return check_device_error(lane);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -5320,6 +5793,66 @@ gpcc_dev_lod_build(
       ctx, params, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_neigh_count,
       (int32_t*)d_neigh_index, (int32_t*)d_neigh_weight, (int32_t*)d_indexes,
       num_points_in_lod, num_lods),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_lift_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, void* d_coeffs, void* d_indexes, const int64_t* ref_offsets, const void* d_xyz_ref,
+  const void* d_attrs_ref, int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    dev_inter_coder_attr<LiftCoder>(
+      ctx, true, lod, lift, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)d_coeffs, (int32_t*)d_indexes, ref_offsets, (const int32_t*)d_xyz_ref, (const int32_t*)d_attrs_ref,
+      search_range, frame_distance),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_lift_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, const void* d_coeffs, void* d_indexes, const int64_t* ref_offsets, const void* d_xyz_ref,
+  const void* d_attrs_ref, int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    dev_inter_coder_attr<LiftCoder>(
+      ctx, false, lod, lift, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)d_coeffs, (int32_t*)d_indexes, ref_offsets, (const int32_t*)d_xyz_ref, (const int32_t*)d_attrs_ref,
+      search_range, frame_distance),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_pred_encode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, void* d_values, void* d_indexes, const int64_t* ref_offsets, const void* d_xyz_ref,
+  const void* d_attrs_ref, int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    dev_inter_coder_attr<PredCoder>(
+      ctx, true, lod, pred, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)d_values, (int32_t*)d_indexes, ref_offsets, (const int32_t*)d_xyz_ref, (const int32_t*)d_attrs_ref,
+      search_range, frame_distance),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_pred_decode_attr_inter(
+  gpcc_ctx* ctx, const gpcc_lod_params* lod, gpcc_pred_params* pred, int32_t num_slices, const int64_t* offsets,
+  const void* d_xyz, void* d_attrs, const void* d_values, void* d_indexes, const int64_t* ref_offsets, const void* d_xyz_ref,
+  const void* d_attrs_ref, int32_t search_range, int32_t frame_distance)
+{
+  return counted(
+    ctx,
+    dev_inter_coder_attr<PredCoder>(
+      ctx, false, lod, pred, num_slices, offsets, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)d_values, (int32_t*)d_indexes, ref_offsets, (const int32_t*)d_xyz_ref, (const int32_t*)d_attrs_ref,
+      search_range, frame_distance),
     batch_points(offsets, num_slices));
 }
 

@@ -197,6 +197,46 @@ class Context:
             self._h, C.byref(params), len(offsets) - 1, off, C.c_void_p(d_xyz), C.c_void_p(d_pos_out),
             C.c_void_p(d_bbox or 0)))
 
+    # ---- the reference frame of an inter-predicted LoD slice -------------
+    def attr_ref_crop(self, xyz, xyz_frame, attrs_frame, capacity=None):
+        """gpcc_attr_ref_crop -> (positions int32 [k, 3], attributes int32 [k, c], bounding box int32 [2, 3] of
+        xyz): the points of the previous frame inside the current slice's bounding box, in order.
+        capacity: the size of the output buffers (None: the frame's, which always suffices)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        fx = np.ascontiguousarray(xyz_frame, dtype=np.int32)
+        fa = np.ascontiguousarray(attrs_frame, dtype=np.int32).reshape(fx.shape[0], -1)
+        nf, c = fa.shape
+        cap = nf if capacity is None else int(capacity)
+        ox = np.zeros((cap, 3), dtype=np.int32)
+        oa = np.zeros((cap, c), dtype=np.int32)
+        k = C.c_int32(-1)
+        bbox = np.zeros((2, 3), dtype=np.int32)
+        _lib.check(self._lib.gpcc_attr_ref_crop(
+            self._h, xyz.ctypes.data, xyz.shape[0], nf, fx.ctypes.data, fa.ctypes.data, c,
+            ox.ctypes.data if cap else None, oa.ctypes.data if cap else None, cap, C.byref(k), bbox.ctypes.data))
+        return ox[:k.value], oa[:k.value], bbox
+
+    def dev_attr_ref_crop(self, offsets, d_xyz, n_frame, d_xyz_frame, d_attrs_frame, c, d_xyz_ref, d_attrs_ref,
+                          capacity, want_bbox=False):
+        """gpcc_dev_attr_ref_crop -> ref_offsets int64 [slices + 1] (and the slices' boxes int32 [slices, 6]):
+        one wait on the context's stream behind the count, the scatter is enqueued.  On a capacity that is too
+        small GpccError is raised with the offsets in its `ref_offsets` attribute."""
+        ns = len(offsets) - 1
+        off = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        ro = np.full(ns + 1, -1, dtype=np.int64)
+        bbox = np.zeros((ns, 6), dtype=np.int32) if want_bbox else None
+        rc = self._lib.gpcc_dev_attr_ref_crop(
+            self._h, ns, off, C.c_void_p(d_xyz), int(n_frame), C.c_void_p(d_xyz_frame), C.c_void_p(d_attrs_frame),
+            int(c), C.c_void_p(d_xyz_ref or 0), C.c_void_p(d_attrs_ref or 0), int(capacity),
+            ro.ctypes.data_as(C.POINTER(C.c_int64)), None if bbox is None else bbox.ctypes.data)
+        if rc != 0:
+            try:
+                _lib.check(rc)
+            except _lib.GpccError as e:
+                e.ref_offsets = ro
+                raise
+        return (ro, bbox) if want_bbox else ro
+
     # ---- lifting transform (predictors given, host tier) -------------------
     @staticmethod
     def _partial(min_geom_node_size_log2, geom_num_points, n):
@@ -363,6 +403,54 @@ class Context:
         """lift_encode_attr_rdo for the predicting transform"""
         return self._encode_attr_rdo(self._lib.gpcc_pred_encode_attr_rdo, lod_inter, lod_intra, pred_params, xyz,
                                      attrs, xyz_ref, attrs_ref, search_range, frame_distance)
+
+    # ---- a slice with attribute inter prediction in one call ----
+    def attr_inter(self, predicting, encode, lod_params, params, xyz, xyz_ref, attrs_ref, search_range,
+                   frame_distance=1, attrs=None, values=None, in_place=False):
+        """gpcc_{lift,pred}_{encode,decode}_attr_inter: the LoD build over the slice and its reference frame and
+        the reflectance transform, the structure left on the device -> (values [n,1] coding order, clipped
+        recon [n,1] point order, indexes [n]); params.num_lods / num_points_in_lod are filled in.
+        in_place: attrs and values are the caller's own int32 C-contiguous arrays of n entries and go to the entry as
+        they are, as a C caller's would (attrs in: source, out: reconstruction; values out, or in for the decoder)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        xyz_ref = np.ascontiguousarray(xyz_ref, dtype=np.int32)
+        ar = np.ascontiguousarray(attrs_ref, dtype=np.int32).reshape(-1)
+        n = xyz.shape[0]
+        if in_place:
+            a, v = attrs, values
+            for buf in (a, v):
+                assert buf.dtype == np.int32 and buf.flags["C_CONTIGUOUS"] and buf.size == n
+        else:
+            a = np.ascontiguousarray(attrs, dtype=np.int32).reshape(n, 1).copy() if encode else np.zeros((n, 1), np.int32)
+            v = (np.zeros((n, 1), np.int32) if encode
+                 else np.ascontiguousarray(values, dtype=np.int32).reshape(n, 1).copy())
+        idx = np.zeros(n, dtype=np.int32)
+        fn = getattr(self._lib, "gpcc_%s_%s_attr_inter" % ("pred" if predicting else "lift",
+                                                             "encode" if encode else "decode"))
+        _lib.check(fn(self._h, C.byref(lod_params), C.byref(params), xyz.ctypes.data, a.ctypes.data, v.ctypes.data,
+                      idx.ctypes.data, n, xyz_ref.ctypes.data, ar.ctypes.data, xyz_ref.shape[0], search_range,
+                      frame_distance))
+        return v, a, idx
+
+    def dev_attr_inter(self, predicting, encode, lod_params, params_list, offsets, d_xyz, d_attrs, d_values,
+                       ref_offsets, d_xyz_ref, d_attrs_ref, search_range, frame_distance=1, d_indexes=None):
+        """gpcc_dev_{lift,pred}_{encode,decode}_attr_inter on device buffers: slice s against the frame segment
+        [ref_offsets[s], ref_offsets[s + 1]) of d_xyz_ref / d_attrs_ref (what dev_attr_ref_crop leaves);
+        params_list: one LiftParams / PredParams per slice (filled with the LoD structure)"""
+        from .params import LiftParams, PredParams
+        P = PredParams if predicting else LiftParams
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        ro = np.ascontiguousarray(ref_offsets, dtype=np.int64)
+        s = len(offs) - 1
+        assert len(ro) == s + 1 and len(params_list) == s
+        arr = (P * s)(*params_list)
+        fn = getattr(self._lib, "gpcc_dev_%s_%s_attr_inter" % ("pred" if predicting else "lift",
+                                                                 "encode" if encode else "decode"))
+        i64p = C.POINTER(C.c_int64)
+        _lib.check(fn(self._h, C.byref(lod_params), arr, s, offs.ctypes.data_as(i64p), d_xyz, d_attrs, d_values,
+                      d_indexes, ro.ctypes.data_as(i64p), d_xyz_ref, d_attrs_ref, search_range, frame_distance))
+        for i in range(s):
+            C.memmove(C.byref(params_list[i]), C.byref(arr[i]), C.sizeof(P))
 
     def estimate_dist2(self, xyz, sampling_period=100, search_range=128, percentile=0.85):
         """pcc::estimateDist2 (encoder.cpp:1203 uses period 100, range 128) -> shift bits"""

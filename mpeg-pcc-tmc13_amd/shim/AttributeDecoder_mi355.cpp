@@ -130,18 +130,15 @@ private:
     std::vector<int32_t> xyz, attrs(size_t(c) * n);
     positions_of(cloud, &xyz);
     int rc;
-    InterStructure is;
+    InterFrame frame;
     if (interSlice) {
-      rc = build_inter_structure(ctx, lod, xyz, n, _first.abh, inter, &is);
+      rc = reference_frame_of(inter, &frame);
       if (!rc && lifting) {
         lp.bitdepth = desc.bitdepth;
         lp.fixed_point_qp_offset = qpSet.fixedPointQpOffset;
-        lp.num_lods = is.nl;
-        for (int l = 0; l < is.nl; l++)
-          lp.num_points_in_lod[l] = is.npl[l];
-        rc = gpcc_lift_inverse_inter(
-          ctx, &lp, n, is.nc.data(), is.ni.data(), is.nw.data(), is.xr.data(), is.idx.data(), attrs.data(),
-          is.attrsFrame.data(), is.nFrame, values.data());
+        rc = gpcc_lift_decode_attr_inter(
+          ctx, &lod, &lp, xyz.data(), attrs.data(), values.data(), nullptr, n, frame.xyz.data(), frame.attrs.data(),
+          frame.n, _first.abh.attrInterPredSearchRange, inter.frameDistance);
       } else if (!rc) {
         pp.bitdepth = desc.bitdepth;
         pp.max_num_direct_predictors = aps.max_num_direct_predictors;
@@ -150,12 +147,9 @@ private:
         for (int k = 0; k < 3; k++)
           pp.quant_neigh_weight[k] = aps.quant_neigh_weight[k];
         pp.max_num_detail_levels = aps.maxNumDetailLevels();
-        pp.num_lods = is.nl;
-        for (int l = 0; l < is.nl; l++)
-          pp.num_points_in_lod[l] = is.npl[l];
-        rc = gpcc_pred_inverse_inter(
-          ctx, &pp, n, is.nc.data(), is.ni.data(), is.nw.data(), is.xr.data(), is.idx.data(), attrs.data(),
-          is.attrsFrame.data(), is.nFrame, values.data());
+        rc = gpcc_pred_decode_attr_inter(
+          ctx, &lod, &pp, xyz.data(), attrs.data(), values.data(), nullptr, n, frame.xyz.data(), frame.attrs.data(),
+          frame.n, _first.abh.attrInterPredSearchRange, inter.frameDistance);
       }
     } else if (lifting) {
       lp.bitdepth = desc.bitdepth;

@@ -12,7 +12,7 @@
 // translation unit, which defines makeAttributeEncoder() with the original
 // signature and returns an AttributeEncoderIntf that
 //   * for a lifting / predicting slice without QP regions (with attribute inter prediction:
-//     one component -- gpcc_lod_build_inter + gpcc_lift_forward_inter / gpcc_pred_forward_inter;
+//     one component -- gpcc_lift_encode_attr_inter / gpcc_pred_encode_attr_inter, one call per slice;
 //     with the slice-level inter / intra decision, attrInterIntraSliceRDO, both candidates in one
 //     call -- gpcc_lift_encode_attr_rdo / gpcc_pred_encode_attr_rdo -- and gpcc_slice_rdo_choose)
 //     runs LoD build + transform (gpcc_lift_encode_attr / gpcc_pred_encode_attr),
@@ -131,8 +131,8 @@ private:
     // ---- LoD build + transform: the values of every predictor in coding order ----
     int8_t lcp[GPCC_MAX_LODS] = {};
     int8_t icp[GPCC_MAX_LODS][3] = {};
-    InterStructure is;
-    if (interSlice && build_inter_structure(ctx, lod, xyz, n, _first.abh, inter, &is))
+    InterFrame frame;
+    if (interSlice && reference_frame_of(inter, &frame))
       return declined();
     if (interSlice && lifting) {
       gpcc_lift_params lp{};
@@ -140,12 +140,9 @@ private:
         return false;
       lp.bitdepth = desc.bitdepth;
       lp.fixed_point_qp_offset = qpSet.fixedPointQpOffset;
-      lp.num_lods = is.nl;
-      for (int l = 0; l < is.nl; l++)
-        lp.num_points_in_lod[l] = is.npl[l];
-      if (gpcc_lift_forward_inter(
-            ctx, &lp, n, is.nc.data(), is.ni.data(), is.nw.data(), is.xr.data(), is.idx.data(), attrs.data(),
-            is.attrsFrame.data(), is.nFrame, values.data()))
+      if (gpcc_lift_encode_attr_inter(
+            ctx, &lod, &lp, xyz.data(), attrs.data(), values.data(), nullptr, n, frame.xyz.data(), frame.attrs.data(),
+            frame.n, _first.abh.attrInterPredSearchRange, inter.frameDistance))
         return declined();
     } else if (interSlice) {
       gpcc_pred_params pp{};
@@ -158,12 +155,9 @@ private:
       for (int k = 0; k < 3; k++)
         pp.quant_neigh_weight[k] = aps.quant_neigh_weight[k];
       pp.max_num_detail_levels = aps.maxNumDetailLevels();
-      pp.num_lods = is.nl;
-      for (int l = 0; l < is.nl; l++)
-        pp.num_points_in_lod[l] = is.npl[l];
-      if (gpcc_pred_forward_inter(
-            ctx, &pp, n, is.nc.data(), is.ni.data(), is.nw.data(), is.xr.data(), is.idx.data(), attrs.data(),
-            is.attrsFrame.data(), is.nFrame, values.data()))
+      if (gpcc_pred_encode_attr_inter(
+            ctx, &lod, &pp, xyz.data(), attrs.data(), values.data(), nullptr, n, frame.xyz.data(), frame.attrs.data(),
+            frame.n, _first.abh.attrInterPredSearchRange, inter.frameDistance))
         return declined();
     } else if (lifting) {
       gpcc_lift_params lp{};

@@ -316,39 +316,28 @@ store_attributes(const std::vector<int32_t>& a, int c, pcc::PCCPointSet3* cloud)
 }
 
 // A slice with attribute inter prediction (one component: the reference's reflectance
-// drivers): the LoD structure with neighbours in the reference frame
-// (gpcc_lod_build_inter) and what the transforms over it need
-struct InterStructure {
-  std::vector<int32_t> nc, ni, nw, idx, xr, attrsFrame;
-  int32_t npl[GPCC_MAX_LODS];
-  int32_t nl = 0;
-  int nFrame = 0;
+// drivers): its reference frame as the gpcc_*_attr_inter entries take it.  The structure
+// with neighbours in that frame is built and used inside those entries: it never leaves
+// the device.
+struct InterFrame {
+  std::vector<int32_t> xyz, attrs;
+  int n = 0;
 };
 
 inline int
-build_inter_structure(
-  gpcc_ctx* ctx, const gpcc_lod_params& lod, const std::vector<int32_t>& xyz, int n,
-  const pcc::AttributeBrickHeader& abh, const pcc::AttributeInterPredParams& inter, InterStructure* s)
+reference_frame_of(const pcc::AttributeInterPredParams& inter, InterFrame* f)
 {
   const auto& frame = inter.referencePointCloud;
-  s->nFrame = int(frame.getPointCount());
-  if (s->nFrame <= 0 || !frame.hasReflectances()) {
+  f->n = int(frame.getPointCount());
+  if (f->n <= 0 || !frame.hasReflectances()) {
     std::fprintf(stderr, "gpcc: the reference frame of this slice has no reflectances; it stays on the CPU\n");
     return GPCC_ERR_UNSUPPORTED;
   }
-  std::vector<int32_t> xyzFrame;
-  positions_of(frame, &xyzFrame);
-  s->attrsFrame.resize(s->nFrame);
-  for (int i = 0; i < s->nFrame; i++)
-    s->attrsFrame[i] = frame.getReflectance(i);
-  s->nc.resize(n);
-  s->ni.resize(size_t(n) * 3);
-  s->nw.resize(size_t(n) * 3);
-  s->idx.resize(n);
-  s->xr.resize(size_t(n) * 3);
-  return gpcc_lod_build_inter(
-    ctx, &lod, xyz.data(), n, xyzFrame.data(), s->nFrame, abh.attrInterPredSearchRange, inter.frameDistance,
-    s->nc.data(), s->ni.data(), s->nw.data(), s->idx.data(), s->npl, &s->nl, s->xr.data());
+  positions_of(frame, &f->xyz);
+  f->attrs.resize(f->n);
+  for (int i = 0; i < f->n; i++)
+    f->attrs[i] = frame.getReflectance(i);
+  return GPCC_OK;
 }
 
 // The context models of an attribute slice by the ids gpcc_binarise_symbols

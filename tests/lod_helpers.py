@@ -235,11 +235,19 @@ def ref_multi_slice_roundtrip(lp_a, transform_a, lp_b, transform_b, qp, offsets,
             [int(v) for v in reused])
 
 
-def oracle_estimate_dist2(xyz, period=100, search_range=128, percentile=0.85):
+def oracle_estimate_dist2(xyz, period=100, search_range=128, percentile=0.85, dists=False):
+    """-> shift bits; dists=True: (shift bits, int64 [samples] nearest squared distance of every sampled
+    point in sample order, INT64_MAX where its window holds no other point; empty when n < 2)"""
     lib = ol.oracle().lib
     xyz = np.ascontiguousarray(xyz, dtype=np.int32)
     lib.oracle_estimate_dist2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
-    return lib.oracle_estimate_dist2(xyz.ctypes.data, xyz.shape[0], period, search_range, C.c_float(percentile), None)
+    n = xyz.shape[0]
+    if not dists:
+        return lib.oracle_estimate_dist2(xyz.ctypes.data, n, period, search_range, C.c_float(percentile), None)
+    out = np.zeros((n + period - 1) // period if n >= 2 else 0, np.int64)
+    shift = lib.oracle_estimate_dist2(xyz.ctypes.data, n, period, search_range, C.c_float(percentile),
+                                      out.ctypes.data if len(out) else None)
+    return shift, out
 
 
 def ref_estimate_dist2(xyz, period=100, search_range=128, percentile=0.85):

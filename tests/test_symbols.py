@@ -111,6 +111,28 @@ def test_device_raht_bitstream_identical_to_reference_operator(case, ctx):
 
 
 @pytest.mark.gpu
+def test_device_packed_symbols_past_the_partition_shape_change(ctx):
+    """the one-call form carves its own workspace for the zero-run kernels: its symbols equal those of the
+    two-call form and the oracle's at 1 048 577 points, where the look-back partition first runs with empty
+    trailing workgroups"""
+    from mpeg_pcc_tmc13_amd import raht_params, synth
+    n = 1048577
+    xyz, attrs = synth.random_cloud(n, seed=61, bits=10, c=1)
+    rp = raht_params(qp=34, chroma_offset=0)
+    co, rec = ctx.raht_encode_attr(rp, xyz, attrs, 16)
+    runs, vals, trailing = ctx.zero_run_pack(co, n, 1, planar=True)
+    o_runs, o_vals, o_tr = lh.oracle_zero_run_pack(co, n, 1, planar=True)
+    np.testing.assert_array_equal(runs, o_runs)
+    np.testing.assert_array_equal(vals, o_vals)
+    assert trailing == o_tr and 0 < len(runs) < n
+    p_runs, p_vals, p_tr, p_rec = ctx.raht_encode_attr_packed(rp, xyz, attrs, 16)
+    np.testing.assert_array_equal(p_runs, runs)
+    np.testing.assert_array_equal(p_vals, vals)
+    assert p_tr == trailing
+    np.testing.assert_array_equal(p_rec, rec)
+
+
+@pytest.mark.gpu
 @needs_ref
 @pytest.mark.parametrize("kind,n,bits", [("dense", 8000, 7), ("lidar", 9000, 0), ("dense", 200000, 10)])
 def test_device_lifting_bitstream_identical_to_reference_operator(kind, n, bits, ctx):

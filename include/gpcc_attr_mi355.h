@@ -1175,6 +1175,21 @@ unsigned long long gpcc_debug_guard_checks(void);
 /* The inter-frame encoder's rate sum (csrc/raht_inter.hpp, rate_sum_kernel) on its own:
  * out[e] = terms[e][0] + terms[e][1] + ... for the two estimates e, doubles added in order. */
 int gpcc_debug_rate_sum(gpcc_ctx* ctx, const double* terms, int32_t count, double out[2]);
+/* The lossy encoder's RDOQ threshold (csrc/raht_levels.hpp) on its own: for case i out_div[i] =
+ * rdoq_threshold(dist2[i], lambda[i], rate_coeff[i], limit[i]) and out_recip[i] = rdoq_threshold_recip
+ * of the same with 1 / lambda formed as the kernels form it.  lambda >= 1, dist2 >= 0. */
+int gpcc_debug_rdoq_threshold(
+  gpcc_ctx* ctx, const int64_t* dist2, const int64_t* lambda, const int32_t* rate_coeff,
+  const uint32_t* limit, int64_t count, uint32_t* out_div, uint32_t* out_recip);
+/* The zero-run resolver (csrc/raht_rdoq.hpp, rdoq_resolve_kernel) on its own.  offsets [S + 1] are
+ * the slices' point offsets; slice s has the ascending, slice-relative cut points
+ * cuts[cut_off[s] .. cut_off[s + 1]), consecutive cuts bounding one level's coefficients, levels in
+ * coding order (fewer than two cuts: no level).  desc [N] are the RDOQ descriptors, coeffs [N][c]
+ * (planar per slice) is resolved in place, slice_l_out [S] receives the last reset carried out of
+ * each slice's last level (-1: none). */
+int gpcc_debug_rdoq_resolve(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const int32_t* cut_off,
+  const int32_t* cuts, const uint32_t* desc, int32_t c, int32_t* coeffs, int32_t* slice_l_out);
 /* With GPCC_GUARD=1: writes 16 bytes past a pooled block (mode 0) or an arena sub-allocation
  * (mode 1) ON PURPOSE -- the process must stop with the guard-band message; without guard mode
  * it does nothing.  tests/test_gpu_guard.py runs it in a child process. */

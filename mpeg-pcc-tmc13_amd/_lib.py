@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "gpcc_dev_pred_encode_attr_inter", "gpcc_dev_pred_decode_attr_inter",
     "gpcc_ctx_reserve",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
+    "gpcc_debug_rdoq_threshold", "gpcc_debug_rdoq_resolve",
     "gpcc_debug_guard_selftest",
 ]
 

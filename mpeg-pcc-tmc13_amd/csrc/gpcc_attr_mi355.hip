@@ -853,10 +853,7 @@ launch_transform(
   std::vector<int32_t> h_off(s + 1), h_rbase(s + 1);
   for (int i = 0; i <= s; i++)
     h_off[i] = (int32_t)offsets[i];
-  h_rbase[0] = 0;
-  for (int i = 0; i < s; i++)
-    h_rbase[i + 1] =
-      h_rbase[i] + (h_off[i + 1] - h_off[i] + kRdoqTile - 1) / kRdoqTile;
+  rdoq_tile_bases(offsets, s, h_rbase.data());
 
   size_t stage_bytes = sizeof(gpcc_raht_params) + 2 * (s + 1) * sizeof(int32_t)
     + 2 * nlev * sizeof(void*) + 64;
@@ -1163,7 +1160,7 @@ launch_transform(
         {
           // one wavefront per 2048-coefficient tile of the batch, in order
           Timer t(ctx, "rdoq_resolve");
-          rdoq_resolve_kernel<<<(pl.num_rtiles + 3) / 4, 256, 0, st>>>(rc);
+          rdoq_resolve_launch(rc, st);
         }
         {
           Timer t(ctx, level_name("tile_synth_rec", li));
@@ -1447,13 +1444,10 @@ dev_transform(
     // (kernel + prepass), headline 12.41 -> 11.77 ms.
     pl.pipe = pipe_on && !encoder && pl.sub && !pl.has_qp && s == 1;
   }
-  pl.num_rtiles = 0;
+  pl.num_rtiles = rdoq_tile_bases(offsets, s, nullptr);
   int64_t n_max = 1;
-  for (int i = 0; i < s; i++) {
-    pl.num_rtiles +=
-      (int)((offsets[i + 1] - offsets[i] + kRdoqTile - 1) / kRdoqTile);
+  for (int i = 0; i < s; i++)
     n_max = std::max(n_max, offsets[i + 1] - offsets[i]);
-  }
   {
     // ArithF64 where B-bit attributes (B from max_qp = 51 + 6 (B - 8), tmc3/quantization.cpp:151)
     // in slices of n points keep every product exact: values reach 2^(B + 15) sqrt(n), the kernels'
@@ -2761,6 +2755,143 @@ gpcc_debug_rate_sum(gpcc_ctx* ctx, const double* terms, int32_t count, double ou
   };
   const int rc = run();
   for (void* p : {d_terms, d_rs, d_err})
+    if (p)
+      pool_free(ctx, p);
+  return rc;
+}
+
+// rdoq_threshold and rdoq_threshold_recip (raht_levels.hpp) alone, for tests/test_gpu_rdoq_edges.py: case i is
+// (dist2[i], lambda[i], rate_coeff[i], limit[i]); out_div / out_recip [count] are the two functions' results
+extern "C" int
+gpcc_debug_rdoq_threshold(
+  gpcc_ctx* ctx, const int64_t* dist2, const int64_t* lambda, const int32_t* rate_coeff, const uint32_t* limit,
+  int64_t count, uint32_t* out_div, uint32_t* out_recip)
+{
+  if (!ctx || count < 0 || count > kMaxPoints
+      || (count > 0 && (!dist2 || !lambda || !rate_coeff || !limit || !out_div || !out_recip)))
+    return fail(GPCC_ERR_INVALID_ARG, "bad arguments");
+  if (count == 0)
+    return GPCC_OK;
+  for (int64_t i = 0; i < count; i++)
+    if (lambda[i] < 1 || lambda[i] > (int64_t)1 << 56 || dist2[i] < 0 || dist2[i] >= (int64_t)1 << 37)
+      return fail(GPCC_ERR_INVALID_ARG, "lambda outside [1, 2^56] or dist2 outside [0, 2^37): the products would wrap");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)count;
+  void *d_d = nullptr, *d_l = nullptr, *d_r = nullptr, *d_m = nullptr, *d_o = nullptr;
+  auto run = [&]() -> int {
+    HIP_TRY(pool_malloc(ctx, &d_d, n * 8));
+    HIP_TRY(pool_malloc(ctx, &d_l, n * 8));
+    HIP_TRY(pool_malloc(ctx, &d_r, n * 4));
+    HIP_TRY(pool_malloc(ctx, &d_m, n * 4));
+    HIP_TRY(pool_malloc(ctx, &d_o, 2 * n * 4));
+    HIP_TRY(h2d_user(ctx, d_d, dist2, n * 8, st));
+    HIP_TRY(h2d_user(ctx, d_l, lambda, n * 8, st));
+    HIP_TRY(h2d_user(ctx, d_r, rate_coeff, n * 4, st));
+    HIP_TRY(h2d_user(ctx, d_m, limit, n * 4, st));
+    hipLaunchKernelGGL(
+      rdoq_threshold_probe_kernel, dim3(grid_for(count, 256)), dim3(256), 0, st, (const int64_t*)d_d,
+      (const int64_t*)d_l, (const int32_t*)d_r, (const uint32_t*)d_m, count, (uint32_t*)d_o, (uint32_t*)d_o + n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(d2h_user(ctx, out_div, d_o, n * 4, st));
+    HIP_TRY(d2h_user(ctx, out_recip, (uint32_t*)d_o + n, n * 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GPCC_OK;
+  };
+  const int rc = run();
+  if (rc != GPCC_OK)
+    hipStreamSynchronize(st);  // (nothing reads the caller's arrays once the call has returned)
+  for (void* p : {d_d, d_l, d_r, d_m, d_o})
+    if (p)
+      pool_free(ctx, p);
+  return rc;
+}
+
+// rdoq_resolve_kernel (raht_rdoq.hpp) alone on the caller's descriptors, for tests/test_gpu_rdoq_edges.py: the
+// levels are given as coefficient ranges (rdoq_probe_plan), state and slice_l start as launch_transform starts
+// them and the kernel is launched as there, once per level from the top one down.  coeffs [N][c] in the
+// planar-per-slice layout is updated in place; slice_l_out [S] is what the last level left.
+extern "C" int
+gpcc_debug_rdoq_resolve(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const int32_t* cut_off, const int32_t* cuts,
+  const uint32_t* desc, int32_t c, int32_t* coeffs, int32_t* slice_l_out)
+{
+  if (!ctx || !offsets || !cut_off || !slice_l_out || num_slices < 1 || c < 1 || c > 3)
+    return fail(GPCC_ERR_INVALID_ARG, "bad arguments");
+  if (cut_off[num_slices] > 0 && !cuts)
+    return fail(GPCC_ERR_INVALID_ARG, "cuts is null");
+  RdoqProbePlan pl;
+  if (!rdoq_probe_plan(offsets, num_slices, cut_off, cuts, &pl))
+    return fail(GPCC_ERR_INVALID_ARG, "offsets / cuts: not ascending, outside the slice, or too many levels");
+  const int s = num_slices;
+  const size_t n = (size_t)offsets[s];
+  if (n > 0 && (!desc || !coeffs))
+    return fail(GPCC_ERR_INVALID_ARG, "desc / coeffs is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  void *d_tab = nullptr, *d_sched = nullptr, *d_desc = nullptr, *d_co = nullptr, *d_state = nullptr, *d_misc = nullptr;
+  auto run = [&]() -> int {
+    // tables: pt_off | tile_base | soff rows, each [s + 1]
+    const size_t row = (size_t)s + 1, rows = 2 + (size_t)pl.nlev + 1;
+    std::vector<int32_t> h_tab(rows * row);
+    std::copy(pl.pt_off.begin(), pl.pt_off.end(), h_tab.begin());
+    std::copy(pl.tile_base.begin(), pl.tile_base.end(), h_tab.begin() + row);
+    std::copy(pl.soff.begin(), pl.soff.end(), h_tab.begin() + 2 * row);
+    HIP_TRY(pool_malloc(ctx, &d_tab, h_tab.size() * 4));
+    HIP_TRY(pool_malloc(ctx, &d_sched, (size_t)s * sizeof(SliceSched)));
+    HIP_TRY(pool_malloc(ctx, &d_desc, std::max<size_t>(n * 4, 16)));
+    HIP_TRY(pool_malloc(ctx, &d_co, std::max<size_t>(n * c * 4, 16)));
+    HIP_TRY(pool_malloc(ctx, &d_state, ((size_t)pl.num_tiles + 1) * sizeof(unsigned long long)));
+    HIP_TRY(pool_malloc(ctx, &d_misc, ((size_t)s + 4) * 4));  // error word (16 bytes), slice_l [s]
+    HIP_TRY(h2d_user(ctx, d_tab, h_tab.data(), h_tab.size() * 4, st));
+    HIP_TRY(h2d_user(ctx, d_sched, pl.sched.data(), (size_t)s * sizeof(SliceSched), st));
+    if (n > 0) {
+      HIP_TRY(h2d_user(ctx, d_desc, desc, n * 4, st));
+      HIP_TRY(h2d_user(ctx, d_co, coeffs, n * c * 4, st));
+    }
+    int32_t* d_err = (int32_t*)d_misc;
+    int32_t* d_sl = d_err + 4;
+    HIP_TRY(hipMemsetAsync(d_err, 0, 16, st));
+    RdoqCtx rc{};
+    rc.tv.nlev = pl.nlev + 1;
+    rc.tv.num_slices = s;
+    rc.tv.n_total = (int32_t)n;
+    rc.tv.pt_off = (const int32_t*)d_tab;
+    for (int li = 0; li <= pl.nlev; li++)
+      rc.tv.soff[li] = (int32_t*)d_tab + (2 + (size_t)li) * row;
+    rc.tv.error = d_err;
+    rc.sched = (const SliceSched*)d_sched;
+    rc.tile_base = (const int32_t*)d_tab + row;
+    rc.num_tiles = pl.num_tiles;
+    rc.desc = (const uint32_t*)d_desc;
+    rc.coeffs = (int32_t*)d_co;
+    rc.slice_l = d_sl;
+    rc.state = (unsigned long long*)d_state;
+    rc.c = c;
+    HIP_TRY(hipMemsetAsync(d_state, 0, ((size_t)pl.num_tiles + 1) * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(d_sl, 0xff, (size_t)s * sizeof(int32_t), st));
+    if (pl.num_tiles > 0)
+      for (int li = pl.nlev - 1; li >= 0; li--) {
+        rc.li = li;
+        rdoq_resolve_launch(rc, st);
+        HIP_TRY(hipGetLastError());
+      }
+    std::vector<int32_t> h_misc((size_t)s + 4);
+    HIP_TRY(d2h_user(ctx, h_misc.data(), d_misc, h_misc.size() * 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_misc[0] != 0)
+      return fail(GPCC_ERR_HIP, "rdoq_resolve_kernel: a look-back wait expired; the result is invalid");
+    if (n > 0) {
+      HIP_TRY(d2h_user(ctx, coeffs, d_co, n * c * 4, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    std::copy(h_misc.begin() + 4, h_misc.end(), slice_l_out);
+    return GPCC_OK;
+  };
+  const int rc = run();
+  if (rc != GPCC_OK)
+    hipStreamSynchronize(st);  // (nothing reads the call's host tables once it has returned)
+  for (void* p : {d_tab, d_sched, d_desc, d_co, d_state, d_misc})
     if (p)
       pool_free(ctx, p);
   return rc;

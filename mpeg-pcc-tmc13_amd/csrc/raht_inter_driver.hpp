@@ -163,7 +163,7 @@ inter_carve(Take&& take, InterWork& w)
     w.rec_us[i] = (int64_t*)arr((size_t)n * c, 8);
     w.nneigh[i] = (int32_t*)arr((size_t)n, 4);
   }
-  w.num_rtiles = (n + kRdoqTile - 1) / kRdoqTile;
+  w.num_rtiles = rdoq_tiles(n);
   if (w.encoder) {
     w.desc = (uint32_t*)arr((size_t)n, 4);
     w.idesc = (uint32_t*)arr((size_t)n, 4);
@@ -806,13 +806,13 @@ inter_run(
         rc.coeffs = d_coeffs;
         rc.slice_l = w.slice_l;
         rc.state = w.rtile_state;
-        hipLaunchKernelGGL(rdoq_resolve_kernel, dim3((w.num_rtiles + 3) / 4), dim3(256), 0, st, rc);
+        rdoq_resolve_launch(rc, st);
         if (dual) {
           rc.desc = w.idesc;
           rc.coeffs = w.icoeffs;
           rc.slice_l = w.islice_l;
           rc.state = w.irtile_state;
-          hipLaunchKernelGGL(rdoq_resolve_kernel, dim3((w.num_rtiles + 3) / 4), dim3(256), 0, st, rc);
+          rdoq_resolve_launch(rc, st);
         }
       }
       if (dual) {

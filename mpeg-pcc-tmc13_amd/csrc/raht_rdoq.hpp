@@ -28,6 +28,9 @@
 // (rdoq_resolve_kernel: one launch per level).
 #pragma once
 
+#include <algorithm>
+#include <vector>
+
 #include "raht_common.hpp"
 #include "raht_levels.hpp"
 
@@ -49,6 +52,29 @@ struct RdoqCtx {
 };
 
 enum { kTileTransparent = 0, kTileClosed = 1, kTileOpen = 2 };
+
+// ---- host side: the tile numbering of a batch --------------------------------------
+// Tiles are counted per slice from its first coefficient, so every slice starts a tile.
+inline int
+rdoq_tiles(int64_t n)
+{
+  return (int)((n + kRdoqTile - 1) / kRdoqTile);
+}
+
+// base[0 .. s] = first global tile of each slice (null: not wanted); returns the batch's tile count
+inline int
+rdoq_tile_bases(const int64_t* offsets, int s, int32_t* base)
+{
+  int t = 0;
+  for (int i = 0; i < s; i++) {
+    if (base)
+      base[i] = t;
+    t += rdoq_tiles(offsets[i + 1] - offsets[i]);
+  }
+  if (base)
+    base[s] = t;
+  return t;
+}
 
 // coefficient range of level li in slice s, slice relative
 __device__ __forceinline__ bool
@@ -285,6 +311,90 @@ rdoq_resolve_kernel(RdoqCtx cx)
           co[(size_t)k * n_s + i] = 0;
       }
     }
+  }
+}
+
+// one launch per level: a wavefront per tile of the batch, four to a workgroup, tiles in launch order
+inline void
+rdoq_resolve_launch(const RdoqCtx& cx, hipStream_t st)
+{
+  hipLaunchKernelGGL(rdoq_resolve_kernel, dim3((cx.num_tiles + 3) / 4), dim3(256), 0, st, cx);
+}
+
+// ---- test support (gpcc_debug_rdoq_resolve, tests/emu): the tables level_coeff_range reads, for levels
+// given as coefficient ranges.  Slice s has the cut points cuts[cut_off[s] .. cut_off[s + 1]), ascending and
+// slice relative: consecutive cuts bound one level, levels in coding order (fewer than two cuts: no processed
+// level).  The j-th level of a slice becomes children level nlev - 1 - j, where nlev is the largest level
+// count of a slice, each a root level of (next cut - cut) nodes, so that m is the level's length; soff is
+// [nlev + 1][S + 1] with a last row of zeros.
+struct RdoqProbePlan {
+  int nlev = 0;
+  int num_tiles = 0;
+  std::vector<int32_t> pt_off, tile_base, soff;
+  std::vector<SliceSched> sched;
+};
+
+inline bool
+rdoq_probe_plan(const int64_t* offsets, int s, const int32_t* cut_off, const int32_t* cuts, RdoqProbePlan* out)
+{
+  RdoqProbePlan& pl = *out;
+  if (s < 1 || offsets[0] != 0 || cut_off[0] != 0)
+    return false;
+  pl.nlev = 0;
+  for (int i = 0; i < s; i++) {
+    const int64_t n_s = offsets[i + 1] - offsets[i];
+    const int nc = cut_off[i + 1] - cut_off[i];
+    if (n_s < 0 || offsets[i + 1] > (int64_t)1 << 30 || nc < 0)
+      return false;
+    for (int j = 0; j < nc; j++) {
+      const int32_t v = cuts[cut_off[i] + j];
+      if (v < 0 || v > n_s || (j > 0 && v <= cuts[cut_off[i] + j - 1]))
+        return false;
+    }
+    pl.nlev = std::max(pl.nlev, nc - 1);
+  }
+  if (pl.nlev > kMaxLevels - 1)
+    return false;
+  pl.pt_off.resize(s + 1);
+  pl.tile_base.resize(s + 1);
+  for (int i = 0; i <= s; i++)
+    pl.pt_off[i] = (int32_t)offsets[i];
+  pl.num_tiles = rdoq_tile_bases(offsets, s, pl.tile_base.data());
+  pl.soff.assign((size_t)(pl.nlev + 1) * (s + 1), 0);
+  pl.sched.assign(s, SliceSched{});
+  for (int i = 0; i < s; i++) {
+    const int nl = cut_off[i + 1] - cut_off[i] - 1;
+    for (int j = 0; j < pl.nlev; j++) {
+      const int li = pl.nlev - 1 - j;
+      int len = 0;
+      if (j < nl) {
+        const int32_t* c0 = cuts + cut_off[i] + j;
+        LevelSched& e = pl.sched[i].lvl[li];
+        e.coeff_base = c0[0];
+        e.processed = 1;
+        e.is_root = 1;
+        len = c0[1] - c0[0];
+      }
+      int32_t* row = pl.soff.data() + (size_t)li * (s + 1);
+      row[i + 1] = row[i] + len;
+    }
+  }
+  return true;
+}
+
+// rdoq_threshold / rdoq_threshold_recip (raht_levels.hpp) on their own, for gpcc_debug_rdoq_threshold: the
+// reciprocal is formed as the kernels that keep it form it (raht_subnode.hpp, cx_level.hpp)
+__global__ __launch_bounds__(256) void
+rdoq_threshold_probe_kernel(
+  const int64_t* dist2, const int64_t* lambda, const int32_t* rate_coeff, const uint32_t* limit, int64_t count,
+  uint32_t* out_div, uint32_t* out_recip)
+{
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const int64_t lam = lambda[i];
+    const double inv_lambda = 1.0 / (double)lam;
+    out_div[i] = rdoq_threshold(dist2[i], lam, rate_coeff[i], limit[i]);
+    out_recip[i] = rdoq_threshold_recip(dist2[i], lam, inv_lambda, rate_coeff[i], limit[i]);
   }
 }
 

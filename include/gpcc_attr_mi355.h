@@ -975,6 +975,39 @@ int gpcc_binarise_symbols(
   int32_t num_symbols, int32_t trailing_run, int32_t c, uint8_t* bins,
   int64_t cap, int64_t* num_bins);
 
+/* The entropy front end of the device tier: gpcc_zero_run_pack and gpcc_binarise_symbols for a BATCH of slices whose
+ * coefficients are in HBM (what every gpcc_dev_*_encode_attr* entry and gpcc_dev_raht_forward leave), and the way
+ * back for the decoders.  Only symbols, decisions and offsets cross PCIe; the number of kernel launches and host
+ * waits does not depend on num_slices; workspace comes from the context's arena (gpcc_ctx_reserve covers it).
+ *
+ * For slice s (n_s points, base b = offsets[s]):
+ *   d_coeffs + c*b : planar != 0 -> [c][n_s] (RAHT), planar == 0 -> [n_s][c] (lifting / predicting)
+ *   bins of slice s: d_bins[bin_offsets[s] .. bin_offsets[s+1]), the bytes gpcc_binarise_symbols gives
+ *   d_runs + b [n_s], d_values + c*b [n_s][c]: symbols of slice s, num_symbols[s] used; both may be NULL
+ *   bin_offsets host [num_slices+1]; num_symbols, trailing_run host [num_slices] (may be NULL)
+ * The call waits ONCE on the context's stream, between counting and emitting, and fills the host arrays in every
+ * case that got that far; the decisions are enqueued behind it and the call returns.
+ * bins_capacity < bin_offsets[num_slices]: GPCC_ERR_INVALID_ARG, the host arrays filled, d_bins untouched.
+ * d_bins == NULL with bins_capacity == 0 is the sizing call: the same path (GPCC_OK only when there is no decision).
+ * Domain: that of the host entries -- c = 1 or 3 (the decisions of a two-component tuple are not defined),
+ * |value| <= 2^31 - 1, at most 2^29 points per batch, a non-empty ordered slice table.  Argument checks run ahead
+ * of the context.  Zero runs never cross a slice: every slice is a stream of its own. */
+int gpcc_dev_residual_bins(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_coeffs,
+  int32_t c, int32_t planar, void* d_bins, int64_t bins_capacity, int64_t* bin_offsets,
+  void* d_runs, void* d_values, int32_t* num_symbols, int32_t* trailing_run);
+
+/* runs / values: HOST arrays, slice s owns symbols [sym_offsets[s], sym_offsets[s+1]); the rest of the slice is zero.
+ * Writes every position of d_coeffs (layout as above), c in 1..3.  Enqueues and returns, like gpcc_dev_raht_inverse:
+ * the symbols have left the caller's arrays when it does.
+ * Symbol k of a slice lies at sum_{j<=k} (runs[j] + 1) - 1.  Nothing is stored outside a slice: a negative run, or
+ * a symbol at or behind position n_s, is not written and sets the context's sticky error word -- the next
+ * gpcc_ctx_synchronize returns GPCC_ERR_INVALID_ARG (the context works afterwards).  A slice with more symbols
+ * than points, null or unordered offsets are refused ahead of the context. */
+int gpcc_dev_zero_run_unpack(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const int64_t* sym_offsets,
+  const int32_t* runs, const int32_t* values, void* d_coeffs, int32_t c, int32_t planar);
+
 /* ------------------------------------------------------------------ */
 /* device tier of the LoD build and the lifting coder                   */
 /* The same operations on buffers resident in HBM, num_slices slices back to

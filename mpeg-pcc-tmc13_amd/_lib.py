@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "gpcc_pred_decode_attr_inter", "gpcc_dev_lift_encode_attr_inter", "gpcc_dev_lift_decode_attr_inter",
     "gpcc_dev_pred_encode_attr_inter", "gpcc_dev_pred_decode_attr_inter",
     "gpcc_ctx_reserve",
+    "gpcc_dev_residual_bins", "gpcc_dev_zero_run_unpack",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_rdoq_threshold", "gpcc_debug_rdoq_resolve",
     "gpcc_debug_guard_selftest",
@@ -179,6 +180,9 @@ def load():
                  "gpcc_multi_pred_decode_attr"):
         getattr(lib, name).argtypes = [vp, C.POINTER(LodParams), vp, i32, i64p, vp, vp, vp, vp, vp, i32]
     lib.gpcc_binarise_symbols.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.c_int64, C.POINTER(C.c_int64)]
+    # the entropy front end of the device tier
+    lib.gpcc_dev_residual_bins.argtypes = [vp, i32, i64p, vp, i32, i32, vp, C.c_int64, i64p, vp, vp, vp, vp]
+    lib.gpcc_dev_zero_run_unpack.argtypes = [vp, i32, i64p, i64p, vp, vp, vp, i32, i32]
     _lib = lib
     return lib
 

@@ -54,6 +54,7 @@
 #include "slice_rdo.hpp"
 #include "spherical.hpp"
 #include "ref_crop.hpp"
+#include "symbol_stream.hpp"
 
 using namespace gpcc;
 
@@ -426,6 +427,67 @@ struct Timer {
     ctx->spans.push_back({name, a, b});
   }
 };
+
+// ---- workspace of the entropy front end (symbol_stream.hpp) ------------
+// With arena.base == nullptr these only measure (gpcc_ctx_reserve, and each call ahead of ensure_arena).
+
+// the slice tables of a batch: pt_off, a second offset table (sym_off; unused by the encoder direction), tile_off
+int32_t*
+sym_carve_meta(Arena& ar, size_t num_slices)
+{
+  return ar.take<int32_t>(3 * (num_slices + 1));
+}
+
+void
+sym_carve(Arena& ar, SymArgs& a, size_t num_slices, size_t num_tiles)
+{
+  a.mask = ar.take<unsigned long long>(num_tiles * kSymWords);
+  a.tile_cnt = ar.take<int32_t>(num_tiles);
+  a.tile_last = ar.take<int32_t>(num_tiles);
+  a.sym_base = ar.take<long long>(num_tiles + 1);
+  a.prev = ar.take<long long>(num_tiles + 1);
+  a.tile_bins = ar.take<int32_t>(num_tiles);
+  a.bin_base = ar.take<long long>(num_tiles + 1);
+  a.scan_sums = ar.take<long long>(sym_scan_blocks(num_tiles));
+  a.scan_maxs = ar.take<long long>(sym_scan_blocks(num_tiles));
+  a.bin_offsets = ar.take<long long>(num_slices + 1);
+  a.num_symbols = ar.take<int32_t>(num_slices);
+  a.trailing_run = ar.take<int32_t>(num_slices);
+}
+
+void
+sym_unpack_carve(Arena& ar, SymUnpackArgs& a, int32_t** d_runs, int32_t** d_values, size_t symbols, int c, size_t num_tiles)
+{
+  *d_runs = ar.take<int32_t>(symbols + 1);
+  *d_values = ar.take<int32_t>((symbols + 1) * c);
+  a.tile_sum = ar.take<long long>(num_tiles + 1);
+  a.tile_base = ar.take<long long>(num_tiles + 1);
+  a.scan_sums = ar.take<long long>(sym_scan_blocks(num_tiles));
+}
+
+// the larger of the two directions for a batch of up to max_points points (as many symbols) in max_slices slices
+size_t
+sym_workspace_bytes(int64_t max_points, int64_t max_slices, int c)
+{
+  const size_t tiles = (size_t)(max_points / kSymTile + max_slices);
+  size_t need = 0;
+  {
+    Arena m;
+    SymArgs a{};
+    sym_carve_meta(m, (size_t)max_slices);
+    sym_carve(m, a, (size_t)max_slices, tiles);
+    need = std::max(need, m.used);
+  }
+  {
+    Arena m;
+    SymUnpackArgs a{};
+    int32_t *r, *v;
+    sym_carve_meta(m, (size_t)max_slices);
+    sym_unpack_carve(m, a, &r, &v, (size_t)max_points, c, tiles);
+    need = std::max(need, m.used);
+  }
+  return need;
+}
 
 // ---- workspace plan ---------------------------------------------------
 
@@ -1324,6 +1386,11 @@ check_device_error(gpcc_ctx* ctx)
         GPCC_ERR_INVALID_ARG,
         "reference frame crop: a coordinate of the frame or of a slice's bounding box outside [0, 2^21); the result "
         "is invalid");
+    if (code == kSymUnpackErrorRange)
+      return fail(
+        GPCC_ERR_INVALID_ARG,
+        "zero-run unpack: a negative run, or a symbol behind the end of its slice; such symbols were not written and "
+        "the result is invalid");
     if (code == 2)
       return fail(
         GPCC_ERR_INVALID_ARG,
@@ -3033,6 +3100,8 @@ gpcc_ctx_reserve(gpcc_ctx* ctx, int64_t max_points, int32_t max_slices, int32_t 
       w);
     need = std::max(need, used);
   }
+  // the entropy front end of the device tier (gpcc_dev_residual_bins, gpcc_dev_zero_run_unpack)
+  need = std::max(need, sym_workspace_bytes(max_points, max_slices, max_c));
   // (GPCC_RESERVE_TOUCH=0: allocate only, do not write the memory -- for measurements)
   static const bool touch = [] {
     const char* e = getenv("GPCC_RESERVE_TOUCH");
@@ -5627,6 +5696,240 @@ gpcc_attr_ref_crop(
   return counted(
     ctx, host_ref_crop(ctx, xyz, n, n_frame, xyz_frame, attrs_frame, c, xyz_ref, attrs_ref, capacity, n_ref, bbox),
     n_frame);
+}
+
+}  // extern "C"
+
+// ---- the entropy front end of the device tier (symbol_stream.hpp) --------------------
+namespace {
+
+// the slice table of a device-tier batch, ahead of the context like every other argument
+int
+check_batch_offsets(int32_t num_slices, const int64_t* offsets)
+{
+  if (num_slices < 1 || !offsets || offsets[0] != 0)
+    return fail(GPCC_ERR_INVALID_ARG, "bad slice offsets");
+  for (int i = 0; i < num_slices; i++)
+    if (offsets[i + 1] <= offsets[i])
+      return fail(GPCC_ERR_INVALID_ARG, "empty or unordered slice");
+  if (offsets[num_slices] > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per batch");
+  return GPCC_OK;
+}
+
+// One wait on the stream, between counting and emitting: bin_offsets, num_symbols and trailing_run (host) are filled
+// as soon as they are known.
+int
+dev_residual_bins(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_coeffs, int32_t c, int32_t planar,
+  void* d_bins, int64_t bins_capacity, int64_t* bin_offsets, void* d_runs, void* d_values, int32_t* num_symbols,
+  int32_t* trailing_run)
+{
+  if (!d_coeffs || !bin_offsets)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  int r = check_batch_offsets(num_slices, offsets);
+  if (r)
+    return r;
+  // (the decisions of a two-component tuple are not defined: gpcc_binarise_symbols refuses it too)
+  if (c != 1 && c != 3)
+    return fail(GPCC_ERR_INVALID_ARG, "bad symbol stream (c must be 1 or 3)");
+  if (bins_capacity < 0 || (bins_capacity > 0 && !d_bins))
+    return fail(GPCC_ERR_INVALID_ARG, "negative capacity or null output buffer");
+  if ((d_runs == nullptr) != (d_values == nullptr))
+    return fail(GPCC_ERR_INVALID_ARG, "d_runs and d_values: both or neither");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  // tiles never straddle a slice (spherical.hpp RplArgs)
+  const size_t S = (size_t)num_slices;
+  std::vector<int32_t> meta(3 * (S + 1), 0);
+  int32_t* h_pt = meta.data();
+  int32_t* h_tile = meta.data() + 2 * (S + 1);
+  for (size_t s = 0; s <= S; s++)
+    h_pt[s] = (int32_t)offsets[s];
+  for (size_t s = 0; s < S; s++)
+    h_tile[s + 1] = h_tile[s] + rpl_tiles(offsets[s + 1] - offsets[s]);
+  const size_t num_tiles = (size_t)h_tile[S];
+
+  SymArgs a{};
+  Arena measure;
+  sym_carve_meta(measure, S);
+  sym_carve(measure, a, S, num_tiles);
+  r = ensure_arena(ctx, measure.used);
+  if (r)
+    return r;
+  Arena& ar = ctx->arena;
+  ar.reset();
+  int32_t* d_meta = sym_carve_meta(ar, S);
+  sym_carve(ar, a, S, num_tiles);
+  HIP_TRY(h2d_user(ctx, d_meta, meta.data(), meta.size() * sizeof(int32_t), st));
+  a.coeffs = (const int32_t*)d_coeffs;
+  a.pt_off = d_meta;
+  a.tile_off = d_meta + 2 * (S + 1);
+  a.runs = (int32_t*)d_runs;
+  a.values = (int32_t*)d_values;
+  a.bins = (uint8_t*)d_bins;
+  a.c = c;
+  a.planar = planar != 0;
+  a.num_slices = num_slices;
+  a.num_tiles = (int32_t)num_tiles;
+  auto span = [&](const char* name) { return Timer(ctx, name); };
+  HIP_TRY(sym_count_launch(st, a, span));
+
+  // the one host wait: the three per-slice arrays through pinned memory -- the context's small block, for a batch
+  // of thousands of slices its bounce buffer (no upload is left in it: both halves are taken)
+  const size_t bytes = (S + 1) * sizeof(int64_t) + 2 * S * sizeof(int32_t);
+  HIP_TRY(small_reset(ctx));
+  char* big = nullptr;
+  char* h = (char*)small_slot(ctx, bytes);
+  if (!h && bytes <= 2 * kBounceBytes) {
+    HIP_TRY(bounce_ready(ctx));
+    HIP_TRY(bounce_take(ctx, 0));
+    HIP_TRY(bounce_take(ctx, 1));
+    h = (char*)ctx->h_bounce;
+  }
+  if (!h) {
+    HIP_TRY(hipHostMalloc((void**)&big, bytes));
+    h = big;
+  }
+  auto wait = [&]() -> int {
+    int64_t* h_off = (int64_t*)h;
+    int32_t* h_sym = (int32_t*)(h + (S + 1) * sizeof(int64_t));
+    int32_t* h_trail = h_sym + S;
+    HIP_TRY(hipMemcpyAsync(h_off, a.bin_offsets, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_sym, a.num_symbols, S * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_trail, a.trailing_run, S * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(bin_offsets, h_off, (S + 1) * sizeof(int64_t));
+    if (num_symbols)
+      memcpy(num_symbols, h_sym, S * sizeof(int32_t));
+    if (trailing_run)
+      memcpy(trailing_run, h_trail, S * sizeof(int32_t));
+    return GPCC_OK;
+  };
+  r = wait();
+  if (big)
+    hipHostFree(big);
+  if (r)
+    return r;
+  if (bin_offsets[num_slices] > bins_capacity)
+    return fail(
+      GPCC_ERR_INVALID_ARG, "the decisions need " + std::to_string(bin_offsets[num_slices]) + " bytes, capacity is "
+        + std::to_string(bins_capacity) + "; nothing was written to d_bins");
+  if (bin_offsets[num_slices] > 0)
+    HIP_TRY(sym_emit_launch(st, a, span));
+  return GPCC_OK;
+}
+
+// enqueues on the context's stream and returns
+int
+dev_zero_run_unpack(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const int64_t* sym_offsets, const int32_t* runs,
+  const int32_t* values, void* d_coeffs, int32_t c, int32_t planar)
+{
+  if (!d_coeffs)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  int r = check_batch_offsets(num_slices, offsets);
+  if (r)
+    return r;
+  if (c < 1 || c > 3)
+    return fail(GPCC_ERR_INVALID_ARG, "attribute count not in 1..3");
+  if (!sym_offsets || sym_offsets[0] != 0)
+    return fail(GPCC_ERR_INVALID_ARG, "bad symbol offsets");
+  for (int s = 0; s < num_slices; s++) {
+    const int64_t m = sym_offsets[s + 1] - sym_offsets[s];
+    if (m < 0)
+      return fail(GPCC_ERR_INVALID_ARG, "unordered symbol offsets");
+    // (every symbol takes a position of its own)
+    if (m > offsets[s + 1] - offsets[s])
+      return fail(GPCC_ERR_INVALID_ARG, "a slice with more symbols than points");
+  }
+  const size_t M = (size_t)sym_offsets[num_slices];
+  if (M > 0 && (!runs || !values))
+    return fail(GPCC_ERR_INVALID_ARG, "null symbol buffer");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  // tiles of symbols that never straddle a slice
+  const size_t S = (size_t)num_slices;
+  std::vector<int32_t> meta(3 * (S + 1), 0);
+  int32_t* h_pt = meta.data();
+  int32_t* h_sym = meta.data() + (S + 1);
+  int32_t* h_tile = meta.data() + 2 * (S + 1);
+  for (size_t s = 0; s <= S; s++) {
+    h_pt[s] = (int32_t)offsets[s];
+    h_sym[s] = (int32_t)sym_offsets[s];
+  }
+  for (size_t s = 0; s < S; s++)
+    h_tile[s + 1] = h_tile[s] + rpl_tiles(sym_offsets[s + 1] - sym_offsets[s]);
+  const size_t num_tiles = (size_t)h_tile[S];
+
+  SymUnpackArgs a{};
+  int32_t *d_runs = nullptr, *d_values = nullptr;
+  Arena measure;
+  sym_carve_meta(measure, S);
+  sym_unpack_carve(measure, a, &d_runs, &d_values, M, c, num_tiles);
+  r = ensure_arena(ctx, measure.used);
+  if (r)
+    return r;
+  Arena& ar = ctx->arena;
+  ar.reset();
+  int32_t* d_meta = sym_carve_meta(ar, S);
+  sym_unpack_carve(ar, a, &d_runs, &d_values, M, c, num_tiles);
+  HIP_TRY(h2d_user(ctx, d_meta, meta.data(), meta.size() * sizeof(int32_t), st));
+  if (M) {
+    HIP_TRY(h2d_user(ctx, d_runs, runs, sizeof(int32_t) * M, st));
+    HIP_TRY(h2d_user(ctx, d_values, values, sizeof(int32_t) * M * c, st));
+  }
+  a.runs = d_runs;
+  a.values = d_values;
+  a.pt_off = d_meta;
+  a.sym_off = d_meta + (S + 1);
+  a.tile_off = d_meta + 2 * (S + 1);
+  a.coeffs = (int32_t*)d_coeffs;
+  a.error = ctx->d_error;
+  a.c = c;
+  a.planar = planar != 0;
+  a.num_slices = num_slices;
+  a.num_tiles = (int32_t)num_tiles;
+  auto span = [&](const char* name) { return Timer(ctx, name); };
+  HIP_TRY(sym_unpack_launch(st, a, (int64_t)c * offsets[num_slices], span));
+  // (the sticky error word travels behind the kernels: the next synchronisation reports it)
+  if (ctx->h_error)
+    HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  return GPCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int
+gpcc_dev_residual_bins(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_coeffs, int32_t c, int32_t planar,
+  void* d_bins, int64_t bins_capacity, int64_t* bin_offsets, void* d_runs, void* d_values, int32_t* num_symbols,
+  int32_t* trailing_run)
+{
+  return counted(
+    ctx,
+    dev_residual_bins(
+      ctx, num_slices, offsets, d_coeffs, c, planar, d_bins, bins_capacity, bin_offsets, d_runs, d_values, num_symbols,
+      trailing_run),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_zero_run_unpack(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const int64_t* sym_offsets, const int32_t* runs,
+  const int32_t* values, void* d_coeffs, int32_t c, int32_t planar)
+{
+  return counted(
+    ctx, dev_zero_run_unpack(ctx, num_slices, offsets, sym_offsets, runs, values, d_coeffs, c, planar),
+    batch_points(offsets, num_slices));
 }
 
 }  // extern "C"

@@ -712,6 +712,43 @@ class Context:
         _lib.check(rc)
         return out[:nb.value].copy()
 
+    # ---- the entropy front end of the device tier --------------------------
+    def dev_residual_bins(self, offsets, d_coeffs, c, planar, d_bins=None, bins_capacity=0, d_runs=None, d_values=None):
+        """gpcc_dev_residual_bins -> (bin_offsets int64 [slices + 1], num_symbols int32 [slices], trailing_run int32
+        [slices]): one wait on the context's stream behind the count, the decisions are enqueued.  d_bins None with
+        capacity 0 only sizes.  On a capacity that is too small GpccError is raised with the three arrays in its
+        `bin_offsets`, `num_symbols` and `trailing_run` attributes."""
+        ns = len(offsets) - 1
+        off = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        bo = np.full(ns + 1, -1, dtype=np.int64)
+        nsym = np.full(ns, -1, dtype=np.int32)
+        trail = np.full(ns, -1, dtype=np.int32)
+        rc = self._lib.gpcc_dev_residual_bins(
+            self._h, ns, off, C.c_void_p(d_coeffs), int(c), int(bool(planar)), C.c_void_p(d_bins or 0), int(bins_capacity),
+            bo.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(d_runs or 0), C.c_void_p(d_values or 0),
+            nsym.ctypes.data, trail.ctypes.data)
+        sizing = not d_bins and int(bins_capacity) == 0 and bo[ns] > 0
+        if rc != 0 and not sizing:
+            try:
+                _lib.check(rc)
+            except _lib.GpccError as e:
+                e.bin_offsets, e.num_symbols, e.trailing_run = bo, nsym, trail
+                raise
+        return bo, nsym, trail
+
+    def dev_zero_run_unpack(self, offsets, sym_offsets, runs, values, d_coeffs, c, planar):
+        """gpcc_dev_zero_run_unpack: the symbols of a batch (host arrays, slice s owns [sym_offsets[s],
+        sym_offsets[s + 1])) to dense coefficients in HBM; enqueued on the context's stream.  A symbol outside its
+        slice is reported by the next synchronize()."""
+        ns = len(offsets) - 1
+        off = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        so = (C.c_int64 * len(sym_offsets))(*[int(o) for o in sym_offsets])
+        r = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+        _lib.check(self._lib.gpcc_dev_zero_run_unpack(
+            self._h, ns, off, so, r.ctypes.data if len(r) else None, v.ctypes.data if len(v) else None,
+            C.c_void_p(d_coeffs), int(c), int(bool(planar))))
+
 
 class MultiContext:
     """gpcc_multi: one context per listed device, slices sharded across them, one

@@ -1193,6 +1193,70 @@ int gpcc_recolour(
   int32_t* tgt_attrs);
 
 /* ------------------------------------------------------------------ */
+/* unique-position quantisation and source partitions                   */
+
+/* What PCCTMC3Encoder3::quantization (encoder.cpp:1554-1577) does to the input cloud in front of the geometry
+ * coder.  All arithmetic is float, formed as the reference forms it: int -> float (round to nearest even), one
+ * multiplication, roundf (halves away from zero), and
+ *   mode 0  quantizePositions (pointset_processing.cpp:170-194): per axis roundf(p * scale) - float(offset) in
+ *           float, converted to int32, clipped to [clamp_min, clamp_max]; every point is kept
+ *   mode 1  quantizePositionsUniq (:143-159): the same positions; points whose results are equal (after the
+ *           clip) merge
+ *   mode 2  samplePositionsUniq (:113-134): positions int(roundf(p * scale)) - offset (an integer subtraction, no
+ *           clip); points merge where int(roundf(roundf(p * scale) * (sample_scale / scale))) is equal, the
+ *           quotient a float division */
+typedef struct gpcc_quantize_params {
+  int32_t mode;         /* 0 quantizePositions, 1 quantizePositionsUniq, 2 samplePositionsUniq */
+  float scale;          /* scaleFactor / quantScale */
+  float sample_scale;   /* mode 2 only */
+  int32_t offset[3];
+  int32_t clamp_min[3], clamp_max[3]; /* modes 0, 1 */
+} gpcc_quantize_params;
+
+/* Host tier, synchronous.  src_xyz [n][3]; dst_xyz [n][3] capacity, the first *num_dst points written;
+ * idx_to_src [n] capacity, *num_dst entries written: SrcMappedPointSet::idxToSrcIdx; src_dup_next [n], all
+ * written: SrcMappedPointSet::srcIdxDupList as reducePointSet (:53-103) returns it.  The source points with equal
+ * keys i0 < i1 < ... < ik have src_dup_next[ij] = i(j+1) and src_dup_next[ik] = ik; the destination cloud holds
+ * one point per group in the order of the first source indices i0, at the position of src[i0]; idx_to_src[d] = i0.
+ * Attributes and laser angles are not touched (the caller gathers laser angles by idx_to_src).
+ * Mode 0 writes dst_xyz only, *num_dst = n; idx_to_src and src_dup_next may be NULL.  n == 0 is accepted.
+ * Domain: n <= 2^29; scale (and sample_scale, and their float quotient) finite and > 0, clamp_min <= clamp_max,
+ * else GPCC_ERR_INVALID_ARG ahead of any launch.  Every float that the reference converts to int32 must lie in
+ * [-2^31, 2^31) -- its conversion is undefined outside: a point outside makes the call fail with
+ * GPCC_ERR_INVALID_ARG (the context's sticky error word; the context works afterwards) and nothing is written to
+ * the caller's buffers.
+ * The call waits once on the context's stream behind the count, then exactly *num_dst positions and map entries
+ * come down.  Workspace comes from the context's arena and pooled buffers; gpcc_ctx_reserve does NOT cover it
+ * (the first call of a size allocates).  There is no device tier: the positions go to the geometry coder on the
+ * host, and gpcc_recolour is host tier. */
+int gpcc_quantize_positions(
+  gpcc_ctx* ctx, const gpcc_quantize_params* params, const int32_t* src_xyz, int32_t n, int32_t* dst_xyz,
+  int32_t* idx_to_src, int32_t* src_dup_next, int32_t* num_dst);
+
+/* getPartition(src, map, indexes) (encoder.cpp:1611-1659) for a batch of slices: for every listed destination
+ * index, in list order, the source points of its group -- the chain from idx_to_src[index] along src_dup_next
+ * until an entry points to itself -- with their positions and attributes.  The output of a slice is what
+ * gpcc_recolour takes as its source cloud.
+ *   src_xyz [n_src][3], src_attrs [n_src][c] (c 1 or 3)
+ *   idx_to_src [n_dst], src_dup_next [n_src]: as gpcc_quantize_positions leaves them
+ *   indexes [index_offsets[num_slices]]: slice s lists indexes[index_offsets[s] .. index_offsets[s + 1]); a
+ *     slice may be empty, an index may repeat
+ *   out_xyz [capacity][3], out_attrs [capacity][c]: the slices back to back, slice s at
+ *     [out_offsets[s], out_offsets[s + 1]); out_offsets host int64 [num_slices + 1]
+ * src_attrs and out_attrs may both be NULL: positions only.  If capacity is too small, or the outputs are NULL
+ * (a call that sizes them): GPCC_ERR_INVALID_ARG with out_offsets filled and nothing written, the convention of
+ * gpcc_attr_ref_crop.  An index outside [0, n_dst), a map entry outside [0, n_src) or a src_dup_next entry that
+ * does not ascend (next[i] > i, or == i at the end of a chain) is refused with GPCC_ERR_INVALID_ARG (validated on
+ * the device as the chains are measured; nothing is written).  At most 2^31 - 1 output points per call.
+ * One wait behind the count; the number of launches does not depend on num_slices.  A chain is walked by one
+ * lane: a group of g points costs g dependent loads.  gpcc_ctx_reserve does not cover the workspace. */
+int gpcc_src_partition(
+  gpcc_ctx* ctx, const int32_t* src_xyz, const int32_t* src_attrs, int32_t n_src, int32_t c,
+  const int32_t* idx_to_src, int32_t n_dst, const int32_t* src_dup_next, const int32_t* indexes,
+  const int32_t* index_offsets, int32_t num_slices, int32_t* out_xyz, int32_t* out_attrs, int64_t capacity,
+  int64_t* out_offsets);
+
+/* ------------------------------------------------------------------ */
 /* debug / test support (exported by every build; nothing an integrator */
 /* needs): used by tests/ and tools/ only                               */
 /* ------------------------------------------------------------------ */

@@ -8,6 +8,7 @@ from . import params, synth  # noqa: F401
 from .params import (LiftParams, LodParams, PredParams, RahtInterParams, RahtParams, RecolourParams, lift_params,  # noqa: F401
                      lod_params, pred_params, raht_params, recolour_params)
 from .params import SphericalParams, spherical_params  # noqa: F401
+from .params import QuantizeParams, quantize_params  # noqa: F401
 
 
 def context(device=0, stream=None):

@@ -3,7 +3,7 @@ if the HIP library is missing or a call fails this module raises."""
 import ctypes as C
 import os
 
-from .params import LiftParams, LodParams, PredParams, RahtParams, SphericalParams
+from .params import LiftParams, LodParams, PredParams, QuantizeParams, RahtParams, SphericalParams
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GPCC_LIB_PATH: an experiment build of the same library (tools/, parameter sweeps)
@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "gpcc_dev_pred_encode_attr_inter", "gpcc_dev_pred_decode_attr_inter",
     "gpcc_ctx_reserve",
     "gpcc_dev_residual_bins", "gpcc_dev_zero_run_unpack",
+    "gpcc_quantize_positions", "gpcc_src_partition",
     "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_rdoq_threshold", "gpcc_debug_rdoq_resolve",
     "gpcc_debug_guard_selftest",
@@ -183,6 +184,9 @@ def load():
     # the entropy front end of the device tier
     lib.gpcc_dev_residual_bins.argtypes = [vp, i32, i64p, vp, i32, i32, vp, C.c_int64, i64p, vp, vp, vp, vp]
     lib.gpcc_dev_zero_run_unpack.argtypes = [vp, i32, i64p, i64p, vp, vp, vp, i32, i32]
+    # unique-position quantisation and the source partitions of a batch of slices
+    lib.gpcc_quantize_positions.argtypes = [vp, C.POINTER(QuantizeParams), vp, i32, vp, vp, vp, C.POINTER(i32)]
+    lib.gpcc_src_partition.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.c_int64, i64p]
     _lib = lib
     return lib
 

@@ -53,6 +53,7 @@
 #include "recolour_kernels.hpp"
 #include "slice_rdo.hpp"
 #include "spherical.hpp"
+#include "quantize_positions.hpp"
 #include "ref_crop.hpp"
 #include "symbol_stream.hpp"
 
@@ -1391,6 +1392,16 @@ check_device_error(gpcc_ctx* ctx)
         GPCC_ERR_INVALID_ARG,
         "zero-run unpack: a negative run, or a symbol behind the end of its slice; such symbols were not written and "
         "the result is invalid");
+    if (code == kQzErrorRange)
+      return fail(
+        GPCC_ERR_INVALID_ARG,
+        "position quantisation: a scaled coordinate outside [-2^31, 2^31), where the reference's conversion to int is "
+        "undefined; nothing was written");
+    if (code == kQzErrorMap)
+      return fail(
+        GPCC_ERR_INVALID_ARG,
+        "source partition: a listed index outside [0, n_dst), a map entry outside [0, n_src) or a duplicate list that "
+        "does not ascend; nothing was written");
     if (code == 2)
       return fail(
         GPCC_ERR_INVALID_ARG,
@@ -5696,6 +5707,285 @@ gpcc_attr_ref_crop(
   return counted(
     ctx, host_ref_crop(ctx, xyz, n, n_frame, xyz_frame, attrs_frame, c, xyz_ref, attrs_ref, capacity, n_ref, bbox),
     n_frame);
+}
+
+}  // extern "C"
+
+// ---- unique-position quantisation and source partitions (quantize_positions.hpp) -----------------
+namespace {
+
+// synchronous; the caller's buffers are written only when the whole call has succeeded
+int
+host_quantize_positions(
+  gpcc_ctx* ctx, const gpcc_quantize_params* p, const int32_t* src_xyz, int32_t n, int32_t* dst_xyz,
+  int32_t* idx_to_src, int32_t* src_dup_next, int32_t* num_dst)
+{
+  if (!p || !num_dst)
+    return fail(GPCC_ERR_INVALID_ARG, "null params or num_dst");
+  if (p->mode < 0 || p->mode > 2)
+    return fail(GPCC_ERR_INVALID_ARG, "mode not in 0..2");
+  if (n < 0 || n > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "n < 0 or more than 2^29 points per call");
+  if (!std::isfinite(p->scale) || !(p->scale > 0))
+    return fail(GPCC_ERR_INVALID_ARG, "scale must be finite and > 0");
+  float diff_scale = 0;
+  if (p->mode == 2) {
+    if (!std::isfinite(p->sample_scale) || !(p->sample_scale > 0))
+      return fail(GPCC_ERR_INVALID_ARG, "sample_scale must be finite and > 0");
+    diff_scale = p->sample_scale / p->scale;  // (float, as samplePositionsUniq divides)
+    if (!std::isfinite(diff_scale) || !(diff_scale > 0))
+      return fail(GPCC_ERR_INVALID_ARG, "sample_scale / scale is not a finite positive float");
+  } else {
+    for (int k = 0; k < 3; k++)
+      if (p->clamp_min[k] > p->clamp_max[k])
+        return fail(GPCC_ERR_INVALID_ARG, "clamp_min > clamp_max");
+  }
+  if (n > 0 && (!src_xyz || !dst_xyz || (p->mode != 0 && (!idx_to_src || !src_dup_next))))
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  if (n == 0) {
+    *num_dst = 0;
+    return GPCC_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  QzArgs a{};
+  QzWork w{};
+  a.n = n;
+  a.mode = p->mode;
+  a.scale = p->scale;
+  a.diff_scale = diff_scale;
+  for (int k = 0; k < 3; k++) {
+    a.offset[k] = p->offset[k];
+    a.clamp_min[k] = p->clamp_min[k];
+    a.clamp_max[k] = p->clamp_max[k];
+  }
+  int max1 = 0, max2 = 0;
+  qz_pass_bounds(p->mode, p->clamp_min, p->clamp_max, &max1, &max2);
+
+  Arena measure;
+  qz_carve([&](size_t bytes) { return measure.take<char>(bytes); }, n, p->mode, a, w);
+  int r = ensure_arena(ctx, measure.used);
+  if (r)
+    return r;
+  Arena& ar = ctx->arena;
+  ar.reset();
+  qz_carve([&](size_t bytes) { return ar.take<char>(bytes); }, n, p->mode, a, w);
+  a.error = ctx->d_error;
+
+  const size_t N = (size_t)n;
+  int32_t* d_src = nullptr;
+  auto run = [&]() -> int {
+    HIP_TRY(pool_malloc(ctx, (void**)&d_src, sizeof(int32_t) * 3 * N));
+    HIP_TRY(h2d_user(ctx, d_src, src_xyz, sizeof(int32_t) * 3 * N, st));
+    a.src = d_src;
+    auto span = [&](const char* name) { return Timer(ctx, name); };
+    HIP_TRY(qz_count_launch(st, a, w, max1, max2, span));
+    // the one host wait: the number of destination points and the error word
+    HIP_TRY(small_reset(ctx));
+    int32_t* h_count = (int32_t*)small_slot(ctx, sizeof(int32_t));
+    if (!h_count)
+      return fail(GPCC_ERR_HIP, "no pinned slot");
+    *h_count = n;
+    if (p->mode != 0)
+      HIP_TRY(hipMemcpyAsync(h_count, w.counts + w.num_tiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (ctx->h_error)
+      HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int r = check_device_error(ctx);
+    if (r)
+      return r;
+    const size_t kept = (size_t)*h_count;
+    if (p->mode == 0) {
+      HIP_TRY(d2h_user(ctx, dst_xyz, a.key, sizeof(int32_t) * 3 * N, st));
+    } else {
+      HIP_TRY(qz_emit_launch(st, a, w, span));
+      HIP_TRY(d2h_user(ctx, dst_xyz, w.dst, sizeof(int32_t) * 3 * kept, st));
+      HIP_TRY(d2h_user(ctx, idx_to_src, w.idx_to_src, sizeof(int32_t) * kept, st));
+      HIP_TRY(d2h_user(ctx, src_dup_next, w.next, sizeof(int32_t) * N, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    *num_dst = (int32_t)kept;
+    return GPCC_OK;
+  };
+  r = run();
+  pool_free(ctx, d_src);
+  return r;
+}
+
+int
+host_src_partition(
+  gpcc_ctx* ctx, const int32_t* src_xyz, const int32_t* src_attrs, int32_t n_src, int32_t c, const int32_t* idx_to_src,
+  int32_t n_dst, const int32_t* src_dup_next, const int32_t* indexes, const int32_t* index_offsets, int32_t num_slices,
+  int32_t* out_xyz, int32_t* out_attrs, int64_t capacity, int64_t* out_offsets)
+{
+  if (!src_xyz || !idx_to_src || !src_dup_next || !index_offsets || !out_offsets)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  if (n_src < 1 || n_src > kMaxPoints || n_dst < 1 || n_dst > n_src)
+    return fail(GPCC_ERR_INVALID_ARG, "n_src not in 1..2^29 or n_dst not in 1..n_src");
+  if (c != 1 && c != 3)
+    return fail(GPCC_ERR_INVALID_ARG, "attribute count is neither 1 nor 3");
+  // (a call without outputs only sizes them)
+  if (out_xyz && (src_attrs == nullptr) != (out_attrs == nullptr))
+    return fail(GPCC_ERR_INVALID_ARG, "src_attrs and out_attrs must both be given or both be null");
+  if (num_slices < 1 || index_offsets[0] != 0)
+    return fail(GPCC_ERR_INVALID_ARG, "num_slices < 1 or index_offsets[0] != 0");
+  for (int s = 0; s < num_slices; s++)
+    if (index_offsets[s + 1] < index_offsets[s])
+      return fail(GPCC_ERR_INVALID_ARG, "index_offsets do not ascend");
+  const int32_t listed = index_offsets[num_slices];
+  if (listed > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 listed indices per call");
+  if (listed > 0 && !indexes)
+    return fail(GPCC_ERR_INVALID_ARG, "null index list");
+  if (capacity < 0 || (capacity > 0 && !out_xyz))
+    return fail(GPCC_ERR_INVALID_ARG, "negative capacity or null output buffer");
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  if (listed == 0) {
+    for (int s = 0; s <= num_slices; s++)
+      out_offsets[s] = 0;
+    return GPCC_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const bool attrs = src_attrs != nullptr && out_attrs != nullptr;
+  const size_t NS = (size_t)n_src, ND = (size_t)n_dst, L = (size_t)listed, S1 = (size_t)num_slices + 1;
+
+  Arena measure;
+  auto carve = [&](Arena& ar, PartArgs& a, long long*& sums) {
+    a.counts = ar.take<int32_t>(L + 1);
+    sums = ar.take<long long>(part_sum_entries(listed));
+    a.total = ar.take<unsigned long long>(1);
+    a.offsets = ar.take<int32_t>(S1);
+  };
+  PartArgs a{};
+  long long* d_sums = nullptr;
+  carve(measure, a, d_sums);
+  int r = ensure_arena(ctx, measure.used);
+  if (r)
+    return r;
+  ctx->arena.reset();
+  carve(ctx->arena, a, d_sums);
+  a.error = ctx->d_error;
+  a.n_src = n_src;
+  a.n_dst = n_dst;
+  a.c = c;
+  a.listed = listed;
+  a.num_slices = num_slices;
+
+  int32_t *d_sx = nullptr, *d_sa = nullptr, *d_map = nullptr, *d_next = nullptr, *d_idx = nullptr, *d_ioff = nullptr;
+  int32_t *d_ox = nullptr, *d_oa = nullptr;
+  int32_t* big = nullptr;
+  auto run = [&]() -> int {
+    HIP_TRY(pool_malloc(ctx, (void**)&d_sx, sizeof(int32_t) * 3 * NS));
+    if (attrs)
+      HIP_TRY(pool_malloc(ctx, (void**)&d_sa, sizeof(int32_t) * c * NS));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_map, sizeof(int32_t) * ND));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_next, sizeof(int32_t) * NS));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_idx, sizeof(int32_t) * L));
+    HIP_TRY(pool_malloc(ctx, (void**)&d_ioff, sizeof(int32_t) * S1));
+    // (the map and the lists first: the count pass needs nothing else)
+    HIP_TRY(h2d_user(ctx, d_map, idx_to_src, sizeof(int32_t) * ND, st));
+    HIP_TRY(h2d_user(ctx, d_next, src_dup_next, sizeof(int32_t) * NS, st));
+    HIP_TRY(h2d_user(ctx, d_idx, indexes, sizeof(int32_t) * L, st));
+    HIP_TRY(h2d_user(ctx, d_ioff, index_offsets, sizeof(int32_t) * S1, st));
+    a.idx_to_src = d_map;
+    a.next = d_next;
+    a.indexes = d_idx;
+    a.index_offsets = d_ioff;
+    auto span = [&](const char* name) { return Timer(ctx, name); };
+    HIP_TRY(part_count_launch(st, a, d_sums, span));
+
+    // the one host wait: the total, the slices' offsets and the error word through pinned memory
+    const size_t words = S1 + 2;
+    HIP_TRY(small_reset(ctx));
+    int32_t* h = (int32_t*)small_slot(ctx, words * sizeof(int32_t));
+    if (!h) {
+      HIP_TRY(hipHostMalloc((void**)&big, words * sizeof(int32_t)));
+      h = big;
+    }
+    HIP_TRY(hipMemcpyAsync(h, a.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h + 2, a.offsets, S1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (ctx->h_error)
+      HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // (the source cloud goes up while the host waits for nothing it needs it for)
+    HIP_TRY(h2d_user(ctx, d_sx, src_xyz, sizeof(int32_t) * 3 * NS, st));
+    if (attrs)
+      HIP_TRY(h2d_user(ctx, d_sa, src_attrs, sizeof(int32_t) * c * NS, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int r = check_device_error(ctx);
+    if (r)
+      return r;
+    unsigned long long total = 0;
+    memcpy(&total, h, sizeof(total));
+    if (total > (unsigned long long)INT32_MAX)
+      return fail(GPCC_ERR_INVALID_ARG, "the partitions hold more than 2^31 - 1 points in one call");
+    for (size_t s = 0; s < S1; s++)
+      out_offsets[s] = h[2 + s];
+    if ((int64_t)total > capacity || !out_xyz)
+      return fail(
+        GPCC_ERR_INVALID_ARG, "the partitions need " + std::to_string(total) + " points, capacity is "
+          + std::to_string(capacity) + "; nothing was written");
+    if (total == 0)
+      return GPCC_OK;
+    const size_t T = (size_t)total;
+    HIP_TRY(pool_malloc(ctx, (void**)&d_ox, sizeof(int32_t) * 3 * T));
+    if (attrs)
+      HIP_TRY(pool_malloc(ctx, (void**)&d_oa, sizeof(int32_t) * c * T));
+    a.src_xyz = d_sx;
+    a.src_attrs = d_sa;
+    a.out_xyz = d_ox;
+    a.out_attrs = attrs ? d_oa : nullptr;
+    HIP_TRY(part_emit_launch(st, a, span));
+    HIP_TRY(d2h_user(ctx, out_xyz, d_ox, sizeof(int32_t) * 3 * T, st));
+    if (attrs)
+      HIP_TRY(d2h_user(ctx, out_attrs, d_oa, sizeof(int32_t) * c * T, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GPCC_OK;
+  };
+  r = run();
+  if (r)
+    hipStreamSynchronize(st);  // (uploads still in flight read the pooled blocks released below)
+  if (big)
+    hipHostFree(big);
+  pool_free(ctx, d_oa);
+  pool_free(ctx, d_ox);
+  pool_free(ctx, d_ioff);
+  pool_free(ctx, d_idx);
+  pool_free(ctx, d_next);
+  pool_free(ctx, d_map);
+  pool_free(ctx, d_sa);
+  pool_free(ctx, d_sx);
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int
+gpcc_quantize_positions(
+  gpcc_ctx* ctx, const gpcc_quantize_params* params, const int32_t* src_xyz, int32_t n, int32_t* dst_xyz,
+  int32_t* idx_to_src, int32_t* src_dup_next, int32_t* num_dst)
+{
+  return counted(ctx, host_quantize_positions(ctx, params, src_xyz, n, dst_xyz, idx_to_src, src_dup_next, num_dst), n);
+}
+
+int
+gpcc_src_partition(
+  gpcc_ctx* ctx, const int32_t* src_xyz, const int32_t* src_attrs, int32_t n_src, int32_t c, const int32_t* idx_to_src,
+  int32_t n_dst, const int32_t* src_dup_next, const int32_t* indexes, const int32_t* index_offsets, int32_t num_slices,
+  int32_t* out_xyz, int32_t* out_attrs, int64_t capacity, int64_t* out_offsets)
+{
+  return counted(
+    ctx,
+    host_src_partition(
+      ctx, src_xyz, src_attrs, n_src, c, idx_to_src, n_dst, src_dup_next, indexes, index_offsets, num_slices, out_xyz,
+      out_attrs, capacity, out_offsets),
+    n_src);
 }
 
 }  // extern "C"

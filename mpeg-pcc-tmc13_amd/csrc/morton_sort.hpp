@@ -53,8 +53,10 @@ morton_encode_kernel(
   }
 }
 
-__global__ __launch_bounds__(kSortThreads) void
-sort_hist_kernel(SortCtx cx)
+// The three passes as device functions: the kernels below are the sort's own; quantize_positions.hpp wraps the
+// same bodies in kernels that take the digit's shift and the buffers from a plan on the device.
+__device__ __forceinline__ void
+sort_hist_pass(const SortCtx& cx)
 {
   __shared__ uint32_t h[256];
   for (int tile = blockIdx.x; tile < cx.num_tiles; tile += gridDim.x) {
@@ -69,11 +71,17 @@ sort_hist_kernel(SortCtx cx)
   }
 }
 
+__global__ __launch_bounds__(kSortThreads) void
+sort_hist_kernel(SortCtx cx)
+{
+  sort_hist_pass(cx);
+}
+
 // Exclusive scan of hist in (slice, digit, tile) order: a key goes after all
 // keys of earlier slices, then smaller digits of its slice, then earlier
 // tiles with the same digit.  One workgroup; slices x 256 digits x tiles.
-__global__ __launch_bounds__(1024) void
-sort_scan_kernel(SortCtx cx)
+__device__ __forceinline__ void
+sort_scan_pass(const SortCtx& cx)
 {
   __shared__ uint32_t wave_tot[16];
   __shared__ uint32_t carry_s;
@@ -116,8 +124,14 @@ sort_scan_kernel(SortCtx cx)
   }
 }
 
-__global__ __launch_bounds__(kSortThreads) void
-sort_scatter_kernel(SortCtx cx)
+__global__ __launch_bounds__(1024) void
+sort_scan_kernel(SortCtx cx)
+{
+  sort_scan_pass(cx);
+}
+
+__device__ __forceinline__ void
+sort_scatter_pass(const SortCtx& cx)
 {
   __shared__ uint32_t digit_base[256];
   __shared__ uint32_t wave_cnt[4][256];  // per wave digit counts of a row
@@ -170,6 +184,12 @@ sort_scatter_kernel(SortCtx cx)
       __syncthreads();
     }
   }
+}
+
+__global__ __launch_bounds__(kSortThreads) void
+sort_scatter_kernel(SortCtx cx)
+{
+  sort_scatter_pass(cx);
 }
 
 // marshalling of the RAHT drivers (AttributeEncoder.cpp:1331-1338,

@@ -347,3 +347,29 @@ def spherical_params(origin, thetas, scale, min_pos_mode=0, min_pos=(0, 0, 0), c
     p.min_pos_mode = int(min_pos_mode)
     p.convert = int(bool(convert))
     return p
+
+
+class QuantizeParams(C.Structure):
+    """ctypes mirror of gpcc_quantize_params: what quantizePositions / quantizePositionsUniq / samplePositionsUniq
+    (pointset_processing.cpp:113-194) take besides the cloud."""
+    _fields_ = [
+        ("mode", C.c_int32),          # 0 keep duplicates, 1 unique quantisation, 2 unique sampling
+        ("scale", C.c_float),
+        ("sample_scale", C.c_float),  # mode 2 only
+        ("offset", C.c_int32 * 3),
+        ("clamp_min", C.c_int32 * 3),
+        ("clamp_max", C.c_int32 * 3),
+    ]
+
+
+def quantize_params(mode, scale, offset=(0, 0, 0), clamp_min=None, clamp_max=None, sample_scale=1.0):
+    """clamp_min / clamp_max None: the whole int32 range (no clip)"""
+    p = QuantizeParams()
+    p.mode = int(mode)
+    p.scale = float(scale)
+    p.sample_scale = float(sample_scale)
+    for k in range(3):
+        p.offset[k] = int(offset[k])
+        p.clamp_min[k] = -(1 << 31) if clamp_min is None else int(clamp_min[k])
+        p.clamp_max[k] = (1 << 31) - 1 if clamp_max is None else int(clamp_max[k])
+    return p

@@ -475,6 +475,73 @@ class Context:
             C.c_float(scale), off, out.ctypes.data))
         return out
 
+    # ---- unique-position quantisation and source partitions ---------------
+    def quantize_positions(self, params, src_xyz, fill=None):
+        """gpcc_quantize_positions -> (dst_xyz int32 [num_dst, 3], idx_to_src int32 [num_dst], src_dup_next int32 [n]);
+        mode 0: (dst_xyz [n, 3], None, None).  fill: what the output buffers hold before the call (tests)."""
+        sx = np.ascontiguousarray(src_xyz, dtype=np.int32).reshape(-1, 3)
+        n = sx.shape[0]
+        v = 0 if fill is None else fill
+        dst = np.full((n, 3), v, dtype=np.int32)
+        uniq = params.mode != 0
+        idx = np.full(n, v, dtype=np.int32) if uniq else None
+        nxt = np.full(n, v, dtype=np.int32) if uniq else None
+        k = C.c_int32(-1)
+        rc = self._lib.gpcc_quantize_positions(
+            self._h, C.byref(params), sx.ctypes.data, n, dst.ctypes.data, idx.ctypes.data if uniq else None,
+            nxt.ctypes.data if uniq else None, C.byref(k))
+        if rc != 0:
+            try:
+                _lib.check(rc)
+            except _lib.GpccError as e:
+                e.buffers = (dst, idx, nxt)
+                raise
+        return (dst[:k.value], idx[:k.value], nxt) if uniq else (dst, None, None)
+
+    def src_partition(self, src_xyz, src_attrs, idx_to_src, src_dup_next, indexes, index_offsets=None, capacity=None):
+        """gpcc_src_partition -> (out_xyz int32 [total, 3], out_attrs int32 [total, c] or None, out_offsets int64
+        [slices + 1]): per listed destination index, in list order, the source points of its group.
+        index_offsets None: one slice.  capacity None: sized by a first call without outputs.  On a capacity that
+        is too small GpccError is raised with the offsets in its `out_offsets` attribute."""
+        sx = np.ascontiguousarray(src_xyz, dtype=np.int32).reshape(-1, 3)
+        ns = sx.shape[0]
+        sa = None if src_attrs is None else np.ascontiguousarray(src_attrs, dtype=np.int32).reshape(ns, -1)
+        c = 1 if sa is None else sa.shape[1]
+        m = np.ascontiguousarray(idx_to_src, dtype=np.int32)
+        nx = np.ascontiguousarray(src_dup_next, dtype=np.int32)
+        ix = np.ascontiguousarray(indexes, dtype=np.int32)
+        io = np.ascontiguousarray([0, len(ix)] if index_offsets is None else index_offsets, dtype=np.int32)
+        slices = len(io) - 1
+        oo = np.full(slices + 1, -1, dtype=np.int64)
+
+        def call(ox, oa, cap):
+            return self._lib.gpcc_src_partition(
+                self._h, sx.ctypes.data, None if sa is None else sa.ctypes.data, ns, c, m.ctypes.data, len(m),
+                nx.ctypes.data, ix.ctypes.data, io.ctypes.data, slices, None if ox is None else ox.ctypes.data,
+                None if oa is None else oa.ctypes.data, cap, oo.ctypes.data_as(C.POINTER(C.c_int64)))
+
+        def fail(rc):
+            try:
+                _lib.check(rc)
+            except _lib.GpccError as e:
+                e.out_offsets = oo
+                raise
+
+        if capacity is None:
+            rc = call(None, None, 0)
+            if oo[-1] < 0:
+                fail(rc)  # (refused before the count)
+            if oo[-1] == 0 and rc == 0:
+                return np.zeros((0, 3), np.int32), None if sa is None else np.zeros((0, c), np.int32), oo
+            capacity = int(oo[-1])
+        ox = np.zeros((max(capacity, 1), 3), dtype=np.int32)
+        oa = None if sa is None else np.zeros((max(capacity, 1), c), dtype=np.int32)
+        rc = call(ox, oa, int(capacity))
+        if rc != 0:
+            fail(rc)
+        total = int(oo[-1])
+        return ox[:total], None if oa is None else oa[:total], oo
+
     # ---- whole slice driver (sort + marshal + transform + clip + scatter) ----
     def raht_encode_attr(self, params, xyz, attrs, bitdepth=8):
         """encode{Colors,Reflectances}TransformRaht minus the entropy loop ->

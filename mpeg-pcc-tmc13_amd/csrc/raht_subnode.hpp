@@ -73,11 +73,27 @@ sub_round_of_ticket(int tk, int cls)
 // s_memtime around the stages of the loop, summed per launch and per level
 // into g_sub_prof, read back with gpcc_debug_sub_prof).  Empty otherwise.
 #ifdef GPCC_SUB_PROF
-__device__ unsigned long long g_sub_prof[16 + 32 * 20];  // [16 + li * 4 + ..] rounds, prologue, loop, iterations; [144 + li * 6 + ..] stage ticks 0-3, idle iterations
+// [16 + li * 4 + ..] rounds, prologue, loop, iterations; [144 + li * 6 + ..] stage ticks 0-3 (0 = the poll part of X), idle iterations;
+// [656 + li * 8 + ..] the mailbox hand-over in front of the poll: executions, trips, cycles; (P) executions whose computing groups awaited
+// nothing / were fed from the mailbox only / took at least one polled granule
+__device__ unsigned long long g_sub_prof[16 + 32 * 28];
 struct SubProf {
   unsigned long long t0 = 0, t1 = 0, last = 0, acc[4] = {0, 0, 0, 0}, iters = 0, idle_iters = 0;
   // finer marks inside (P) and (W): [336 + li * 10 + ..] P executions, W executions, then the sub-steps' cycles
   unsigned long long last2 = 0, sub_acc[6] = {0, 0, 0, 0, 0, 0}, execs[2] = {0, 0};
+  unsigned long long walk_acc = 0, walk_execs = 0, walk_trips = 0, fed[3] = {0, 0, 0};
+  // the hand-over's share of X (the rest, up to mark<0>, is the poll part); trips: wave-uniform
+  __device__ void walk_end(bool ran, int trips)
+  {
+    if (!ran)
+      return;  // (its test stays with the poll part)
+    const unsigned long long t = now();
+    walk_acc += t - last;
+    last = t;
+    walk_execs += ran;
+    walk_trips += trips;
+  }
+  __device__ void fed_by(bool any_poll, bool any_mailbox) { fed[any_poll ? 2 : (any_mailbox ? 1 : 0)]++; }
   template<int WHICH> __device__ void enter() { execs[WHICH]++; last2 = now(); }
   template<int K> __device__ void sub() { const unsigned long long t = now(); sub_acc[K] += t - last2; last2 = t; }
   __device__ static unsigned long long now() { return __builtin_amdgcn_s_memtime(); }
@@ -105,6 +121,11 @@ struct SubProf {
     atomicAdd(&g_sub_prof[336 + li * 10 + 1], execs[1]);
     for (int i = 0; i < 6; i++)
       atomicAdd(&g_sub_prof[336 + li * 10 + 2 + i], sub_acc[i]);
+    atomicAdd(&g_sub_prof[656 + li * 8 + 0], walk_execs);
+    atomicAdd(&g_sub_prof[656 + li * 8 + 1], walk_trips);
+    atomicAdd(&g_sub_prof[656 + li * 8 + 2], walk_acc);
+    for (int i = 0; i < 3; i++)
+      atomicAdd(&g_sub_prof[656 + li * 8 + 3 + i], fed[i]);
   }
 };
 #else
@@ -116,6 +137,7 @@ struct SubProf {
   template<int WHICH> __device__ void enter() {}
   template<int K> __device__ void sub() {}
   __device__ void idle() {}
+  __device__ void walk_end(bool, int) {}
   __device__ void round_end(int, int) {}
 };
 #endif
@@ -153,6 +175,16 @@ sub_claim_rounds(bool encoder, bool haar, int64_t parents)
   return 1;
 #endif
 }
+
+#ifdef GPCC_EMU
+// What the emulator's tests read back to see that their inputs exercise the in-wavefront hand-over of
+// raht_level_sub_kernel: the most groups of a round that committed in one iteration, and the most slots one
+// lane took from the mailbox in one hand-over.
+extern "C" {
+inline int gpcc_emu_sub_max_commits = 0;
+inline int gpcc_emu_sub_max_taken = 0;
+}
+#endif
 
 __device__ __forceinline__ int
 occu_shift(int i12)
@@ -820,9 +852,12 @@ raht_level_sub_kernel(LevelCtx ctx)
     uint32_t pend = 0;       // neighbours whose child granule is awaited (row of that child: GPCC_SUB_NROW)
     // A neighbour block claimed by THIS wavefront in this round (about 70 % of
     // the hops on the longest chains: Morton-adjacent blocks) hands its
-    // children over through registers instead of a memory round trip:
-    // inw = awaited neighbours of that kind, wsrc = their group, 3 bits each.
-    uint32_t inw = 0, wsrc_a = 0, wsrc_b = 0;
+    // children over through the wavefront's mailbox instead of a memory round trip:
+    // inw = awaited neighbours of that kind.  Each awaited slot belongs to a distinct
+    // neighbour parent, so from one producer group (0..6: a consumer awaits lower
+    // blocks only) a lane awaits at most ONE slot -- wtab, four bits per producer
+    // group: the slot + 1 (0: none).
+    uint32_t inw = 0, wtab = 0;
     int jg[8];
 #pragma unroll
     for (int g = 0; g < 8; g++)
@@ -871,10 +906,7 @@ raht_level_sub_kernel(LevelCtx ctx)
               pg = q == jg[g] ? g : pg;
             if (pg >= 0) {
               inw |= 1u << i12;
-              if (i12 < 10)
-                wsrc_a |= (uint32_t)pg << (3 * i12);
-              else
-                wsrc_b |= (uint32_t)pg << (3 * (i12 - 10));
+              wtab |= (uint32_t)(i12 + 1) << (4 * pg);
             }
           }
         } else {
@@ -943,10 +975,14 @@ raht_level_sub_kernel(LevelCtx ctx)
     int need = 0;           // reach of the block's thresholds before its first coefficient
     int look = wi - 1;      // look-back cursor
     int outk = 0, outv = -1;   // outgoing RDOQ state: 0 unknown, 1 transparent, 2 final (= outv)
-    unsigned long long done = 0;  // children of this round whose value lies in the mailbox (wave-uniform)
-    unsigned long long done_seen = ~0ull;  // `done` when the mailbox loop last ran
+    // groups of this round that have committed since the hand-over last ran, by their first lane (wave-uniform): a group
+    // commits all its children in one iteration, so their values lie in the mailbox
+    unsigned long long newg = 0;
     int cur_slot = -1, cur_pwc = 0;        // the granule this lane polls: slot, weight, row -- looked up when the slot changes
     int32_t cur_row = 0;
+#ifdef GPCC_SUB_PROF
+    bool got_mb = false, got_poll = false;  // this lane took a value from the mailbox / a polled granule
+#endif
 #pragma unroll
     for (int k = 0; k < C; k++) {
       pt[k] = A::zero();
@@ -963,32 +999,46 @@ raht_level_sub_kernel(LevelCtx ctx)
       bool progressed = false;
       prof.iter_begin();
       // ---- (X) awaited children of blocks of this wavefront: the mailbox ----
-      // (only when the mailbox has gained a child since the loop last ran: nothing else lets it consume one, and a waiting
-      // iteration -- a round waits for ~100 of them -- is then the poll below and a handful of tests)
-      if (done != done_seen) {
-        done_seen = done;
-        uint32_t mi = stage == 0 ? (pend & inw) : 0u;
-        while (__any(mi != 0)) {
-          const bool act = mi != 0;
-          const int slot = act ? __ffs(mi) - 1 : 0;
-          mi &= mi - 1;
-          const uint32_t pg = (slot < 10 ? wsrc_a >> (3 * slot) : wsrc_b >> (3 * (slot - 10))) & 7u;
-          // occuShift of findNeighbours (tmc3/RAHT.cpp:377), three bits each
-          constexpr unsigned long long kShifts = 06ull | 05ull << 3 | 04ull << 6 | 03ull << 9 | 02ull << 12
-            | 01ull << 15 | 03ull << 18 | 01ull << 21 | 02ull << 24 | 01ull << 27 | 02ull << 30 | 03ull << 33;
-          const int sh = (int)((kShifts >> (3 * slot)) & 7);
-          const int srcl = (int)(pg << 3) | ((slot < 9 ? t + sh : t - sh) & 7);
-          if (act && ((done >> srcl) & 1)) {
-            const int pwc = GPCC_SUB_PWC(slot);
-            const int mul = ext ? pwc : (pwc << kFpFrac);
+      // (only when a group has committed since the loop last ran: nothing else lets the mailbox feed one, and a waiting
+      // iteration -- a round waits for ~100 of them -- is then the poll below and a handful of tests.)  One trip per newly
+      // committed group, usually one: the loop is scalar, and a lane looks up the one slot it awaits from that group.
+      int prof_trips = 0;
+      const bool prof_ran = newg != 0;
+#ifdef GPCC_EMU
+      int emu_taken = 0;
+#endif
+      while (newg) {
+        const int gl = __ffsll((long long)newg) - 1;  // the group's first lane: 8 g
+        newg &= newg - 1;
+        prof_trips++;
+        const uint32_t s1 = (wtab >> (gl >> 1)) & 15u;
+        const uint32_t bit = (1u << s1) >> 1;  // (none: no bit)
+        if (pend & bit) {
+          // the awaited child's position in its block: t + occuShift of findNeighbours (tmc3/RAHT.cpp:377) for the slots
+          // below 9, t - occuShift for the others, modulo 8 -- three bits per slot + 1
+          constexpr unsigned long long kDelta = 06ull << 3 | 05ull << 6 | 04ull << 9 | 03ull << 12 | 02ull << 15 | 01ull << 18
+            | 03ull << 21 | 01ull << 24 | 02ull << 27 | 07ull << 30 | 06ull << 33 | 05ull << 36;
+          const int srcl = gl | ((t + (int)(kDelta >> (3 * s1))) & 7);
+          const int pwc = GPCC_SUB_PWC((int)s1 - 1);
+          const int mul = ext ? pwc : (pwc << kFpFrac);
 #pragma unroll
-            for (int k = 0; k < C; k++)
-              pred[k] += A::muli(__builtin_bit_cast(VT, wm[srcl * C + k]), mul);
-            pend &= ~(1u << slot);
-            inw &= ~(1u << slot);
-          }
+          for (int k = 0; k < C; k++)
+            pred[k] += A::muli(__builtin_bit_cast(VT, wm[srcl * C + k]), mul);
+          pend &= ~bit;
+          inw &= ~bit;
+#ifdef GPCC_SUB_PROF
+          got_mb = true;
+#endif
+#ifdef GPCC_EMU
+          emu_taken++;
+#endif
         }
       }
+#ifdef GPCC_EMU
+      if (emu_taken > gpcc_emu_sub_max_taken)
+        gpcc_emu_sub_max_taken = emu_taken;
+#endif
+      prof.walk_end(prof_ran, prof_trips);
       // ---- (X) the others: the granule is data and flag at once -----------
       // One granule per lane and iteration -- the lowest awaited one -- so an
       // iteration costs ONE memory round trip however many different
@@ -1035,6 +1085,9 @@ raht_level_sub_kernel(LevelCtx ctx)
             for (int k = 0; k < C; k++)
               pred[k] += A::muli(__builtin_bit_cast(VT, ((uint64_t)g[k].y << 32) | g[k].x), mul);
             pend &= ~(1u << cur_slot);
+#ifdef GPCC_SUB_PROF
+            got_poll = true;
+#endif
           }
         }
         return ok;
@@ -1064,6 +1117,12 @@ raht_level_sub_kernel(LevelCtx ctx)
         progressed = true;
         // ---- (P) normalise the prediction, transform -----------------------
         prof.template enter<0>();
+#ifdef GPCC_SUB_PROF
+        {
+          const bool gp = group8_any(got_poll), gm = group8_any(got_mb);
+          prof.fed_by(__any(nready && gp), __any(nready && gm));
+        }
+#endif
         VT pw_[C];
 #pragma unroll
         for (int k = 0; k < C; k++)
@@ -1477,7 +1536,11 @@ raht_level_sub_kernel(LevelCtx ctx)
           stage = 3;
       }
 
-      done |= __ballot(can && has);
+      newg |= __ballot(can && t == 0);
+#ifdef GPCC_EMU
+      if (__popcll(newg) > gpcc_emu_sub_max_commits)
+        gpcc_emu_sub_max_commits = __popcll(newg);
+#endif
       prof.mark<3>();
       if (!progressed) {
         prof.idle();

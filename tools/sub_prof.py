@@ -32,7 +32,7 @@ src = torch.from_numpy(np.concatenate([a for m, a in fr]).reshape(-1)).to(dev)
 d_a = torch.empty_like(src)
 d_c = torch.zeros(int(offs[-1]), dtype=torch.int32, device=dev)
 lib = _lib.load()
-out = (C.c_ulonglong * (16 + 32 * 20))()
+out = (C.c_ulonglong * (16 + 32 * 28))()  # sizeof(g_sub_prof), raht_subnode.hpp
 ctx.set_morton_bits(54)
 import time
 for it in range(3):
@@ -57,3 +57,9 @@ for li in range(0, 14):
     r = v[16 + li * 4]
     if r:
         print(f"  level {li:2d}: rounds {r:8d} prologue {v[17 + li * 4] / r:9.0f} loop {v[18 + li * 4] / r:9.0f} iterations {v[19 + li * 4] / r:6.2f}")
+        # stage X per round, split: the mailbox hand-over in front of the poll, and the poll part (issue, waiting iterations' answer)
+        h = 656 + li * 8
+        he, pe = max(1, v[h]), max(1, v[336 + li * 10])
+        print(f"            X per round: hand-over {v[h + 2] / r:7.0f} + poll {v[144 + li * 6] / r:7.0f} ticks | hand-over x {v[h] / r:5.2f} per round, "
+              f"{v[h + 1] / he:5.2f} trips and {v[h + 2] / he:6.0f} ticks each | (P) x {v[336 + li * 10] / r:5.2f} per round: "
+              f"{100 * v[h + 3] / pe:4.1f} % awaited nothing, {100 * v[h + 4] / pe:4.1f} % fed from the mailbox only, {100 * v[h + 5] / pe:4.1f} % took a polled granule")

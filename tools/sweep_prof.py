@@ -32,7 +32,7 @@ src = torch.from_numpy(np.concatenate([a for m, a in fr]).reshape(-1)).to(dev)
 d_a = torch.empty_like(src)
 d_c = torch.zeros(int(offs[-1]), dtype=torch.int32, device=dev)
 lib = _lib.load()
-out = (C.c_ulonglong * (16 + 32 * 20))()
+out = (C.c_ulonglong * (16 + 32 * 28))()  # sizeof(g_sub_prof), raht_subnode.hpp
 ctx.set_morton_bits(54)
 import time
 for it in range(3):

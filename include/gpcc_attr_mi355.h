@@ -1265,6 +1265,9 @@ int gpcc_src_partition(
  * misses of the pooled device buffers, out[2] / out[3] (re)allocations of the pinned staging of
  * the compact level pass / of the level kernels.  A steady loop shows none. */
 int gpcc_debug_alloc_events(const gpcc_ctx* ctx, long long out[4]);
+/* Pooled device buffers that are taken at this moment, the lanes of the device tier included:
+ * out[0] blocks, out[1] their bytes.  Between calls both are 0: a call returns every block it took. */
+int gpcc_debug_pool_in_use(const gpcc_ctx* ctx, long long out[2]);
 /* 1 when the library was built with -DGPCC_EXPERIMENTS=1 (opt-in kernel variants compiled in). */
 int gpcc_debug_has_experiments(void);
 /* Guard bands compared so far in this process (0 unless GPCC_GUARD=1 in the environment). */

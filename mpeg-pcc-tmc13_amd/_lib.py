@@ -41,7 +41,7 @@ ABI_SYMBOLS = [
     "gpcc_ctx_reserve",
     "gpcc_dev_residual_bins", "gpcc_dev_zero_run_unpack",
     "gpcc_quantize_positions", "gpcc_src_partition",
-    "gpcc_debug_alloc_events", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
+    "gpcc_debug_alloc_events", "gpcc_debug_pool_in_use", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_rdoq_threshold", "gpcc_debug_rdoq_resolve",
     "gpcc_debug_guard_selftest",
 ]

@@ -24,6 +24,7 @@
 #include <dlfcn.h>
 #include <cstring>
 #include <atomic>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -664,6 +665,37 @@ pool_free(gpcc_ctx* ctx, void* p)
     }
 }
 
+// The pool blocks a call holds: taken through the scope, back in the pool when the scope ends -- on every
+// return path, with the context valid and its device current as when they were taken.  A block that is
+// needed for a part of the call only lives in a scope of that part.
+class PoolScope {
+public:
+  explicit PoolScope(gpcc_ctx* ctx) : ctx_(ctx) {}
+  PoolScope(const PoolScope&) = delete;
+  PoolScope& operator=(const PoolScope&) = delete;
+  ~PoolScope()
+  {
+    for (void* p : held_)
+      pool_free(ctx_, p);
+  }
+  hipError_t take_bytes(size_t bytes, void** out)
+  {
+    hipError_t e = pool_malloc(ctx_, out, bytes);
+    if (e == hipSuccess)
+      held_.push_back(*out);
+    return e;
+  }
+  template<typename T>
+  hipError_t take(size_t count, T** out)
+  {
+    return take_bytes(count * sizeof(T), (void**)out);
+  }
+
+private:
+  gpcc_ctx* ctx_;
+  std::vector<void*> held_;
+};
+
 // A result for the caller's (pageable) memory.  An asynchronous copy straight into pageable
 // memory makes the runtime pin the caller's pages on the fly, and it keeps such pins: a range it
 // has pinned READ-ONLY once, as the source of an upload, is not pinned again when the same
@@ -1102,7 +1134,8 @@ launch_transform(
     // bounds before the tree exists: 12 levels of N nodes for a lidar frame)
     const size_t need = (size_t)total * (4 + 1 + 4 + 32 * C) + 2048;
     void* pipe_mem = nullptr;
-    if (total * C * 16 < ((int64_t)1 << 31) && pool_malloc(ctx, &pipe_mem, need) == hipSuccess) {
+    PoolScope pipe_pool(ctx);  // back in the pool behind the walk: reuse is ordered on the context's stream
+    if (total * C * 16 < ((int64_t)1 << 31) && pipe_pool.take_bytes(need, &pipe_mem) == hipSuccess) {
       Arena pa;
       pa.base = (char*)pipe_mem;
       pa.cap = need;
@@ -1138,7 +1171,6 @@ launch_transform(
         pipe_leaf_kernel<C><<<grid_for(ts.nodes[0], 256), 256, 0, st>>>(lc, px);
       }
       piped = true;
-      pool_free(ctx, pipe_mem);  // reuse is ordered on the context's stream
     }
   }
 
@@ -1581,21 +1613,18 @@ host_transform(
   hipStream_t st = ctx->stream;
   const int bits = bitlen64((uint64_t)(morton[0] ^ morton[n - 1]));
 
-  int64_t* d_m = nullptr;
-  int32_t *d_q = nullptr, *d_a = nullptr, *d_c = nullptr;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_m);
-    pool_free(ctx, d_q);
-    pool_free(ctx, d_a);
-    pool_free(ctx, d_c);
-  };
+  const size_t N = (size_t)n;
+  // one attempt (its blocks are back in the pool when it returns)
   auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_m, sizeof(int64_t) * n));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_a, sizeof(int32_t) * n * c));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_c, sizeof(int32_t) * n * c));
+    PoolScope pool(ctx);
+    int64_t* d_m = nullptr;
+    int32_t *d_q = nullptr, *d_a = nullptr, *d_c = nullptr;
+    HIP_TRY(pool.take(N, &d_m));
+    HIP_TRY(pool.take(N * c, &d_a));
+    HIP_TRY(pool.take(N * c, &d_c));
     HIP_TRY(h2d_user(ctx, d_m, morton, sizeof(int64_t) * n, st));
     if (qp_off) {
-      HIP_TRY(pool_malloc(ctx, (void**)&d_q, sizeof(int32_t) * n * 2));
+      HIP_TRY(pool.take(N * 2, &d_q));
       HIP_TRY(h2d_user(ctx, d_q, qp_off, sizeof(int32_t) * n * 2, st));
     }
     if (encoder) {
@@ -1626,14 +1655,10 @@ host_transform(
   int r = run();
   if (r == GPCC_ERR_RANGE) {
     // the caller's buffers are untouched: once more in int64 arithmetic
-    cleanup();
-    d_m = nullptr;
-    d_q = d_a = d_c = nullptr;
     ctx->force_exact = true;
     r = run();
     ctx->force_exact = false;
   }
-  cleanup();
   return r;
 }
 
@@ -1745,27 +1770,19 @@ host_transform_inter(
       return (char*)nullptr;
     },
     w);
-  char* work = nullptr;
-  int64_t* d_m = nullptr;
-  int64_t* d_mr = nullptr;
-  int32_t *d_a = nullptr, *d_c = nullptr, *d_ar = nullptr, *d_q = nullptr;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_q);
-    pool_free(ctx, work);
-    pool_free(ctx, d_m);
-    pool_free(ctx, d_mr);
-    pool_free(ctx, d_a);
-    pool_free(ctx, d_c);
-    pool_free(ctx, d_ar);
-  };
+  // one attempt (its blocks are back in the pool when it returns)
   auto run = [&]() -> int {
+    PoolScope pool(ctx);
+    char* work = nullptr;
+    int64_t *d_m = nullptr, *d_mr = nullptr;
+    int32_t *d_a = nullptr, *d_c = nullptr, *d_ar = nullptr, *d_q = nullptr;
     HIP_TRY(small_reset(ctx));
-    HIP_TRY(pool_malloc(ctx, (void**)&work, need + 256));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_m, sizeof(int64_t) * n));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_mr, sizeof(int64_t) * n_ref));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_a, sizeof(int32_t) * n * c));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_c, sizeof(int32_t) * n * c));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_ar, sizeof(int32_t) * (size_t)n_ref * c));
+    HIP_TRY(pool.take(need + 256, &work));
+    HIP_TRY(pool.take((size_t)n, &d_m));
+    HIP_TRY(pool.take((size_t)n_ref, &d_mr));
+    HIP_TRY(pool.take((size_t)n * c, &d_a));
+    HIP_TRY(pool.take((size_t)n * c, &d_c));
+    HIP_TRY(pool.take((size_t)n_ref * c, &d_ar));
     size_t off = 0;
     inter_carve(
       [&](size_t bytes) {
@@ -1780,7 +1797,7 @@ host_transform_inter(
     HIP_TRY(h2d_user(ctx, d_mr, morton_ref, sizeof(int64_t) * n_ref, st));
     HIP_TRY(h2d_user(ctx, d_ar, attrs_ref, sizeof(int32_t) * (size_t)n_ref * c, st));
     if (qp_off) {
-      HIP_TRY(pool_malloc(ctx, (void**)&d_q, sizeof(int32_t) * (size_t)n * 2));
+      HIP_TRY(pool.take((size_t)n * 2, &d_q));
       HIP_TRY(h2d_user(ctx, d_q, qp_off, sizeof(int32_t) * (size_t)n * 2, st));
       HIP_TRY(small_h2d(ctx, w.asc_qp_tab, w.asc_qp, sizeof(w.asc_qp), st));
     }
@@ -1847,14 +1864,9 @@ host_transform_inter(
   int r = run();
   if (r == GPCC_ERR_RANGE && w.f64) {
     // the caller's buffers are untouched: once more in int64 arithmetic
-    cleanup();
-    work = nullptr;
-    d_m = d_mr = nullptr;
-    d_a = d_c = d_ar = d_q = nullptr;
     w.f64 = false;
     r = run();
   }
-  cleanup();
   return r;
 }
 
@@ -2778,6 +2790,27 @@ gpcc_debug_alloc_events(const gpcc_ctx* ctx, long long out[4])
   return GPCC_OK;
 }
 
+// {pool blocks a call holds at this moment, their bytes}, the lanes' included: {0, 0} between calls
+extern "C" int
+gpcc_debug_pool_in_use(const gpcc_ctx* ctx, long long out[2])
+{
+  if (!ctx || !out)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx / out is null");
+  out[0] = out[1] = 0;
+  for (auto& b : ctx->pool)
+    if (b.used) {
+      out[0]++;
+      out[1] += (long long)b.cap;
+    }
+  for (const gpcc_ctx* lane : ctx->lanes) {
+    long long l[2];
+    gpcc_debug_pool_in_use(lane, l);
+    out[0] += l[0];
+    out[1] += l[1];
+  }
+  return GPCC_OK;
+}
+
 // 1: the library was built with the round-5 experiments compiled in (GPCC_LINKS / GPCC_SUB_CLAIM work)
 extern "C" int
 gpcc_debug_has_experiments(void)
@@ -2801,41 +2834,34 @@ gpcc_debug_rate_sum(gpcc_ctx* ctx, const double* terms, int32_t count, double ou
     return fail(GPCC_ERR_INVALID_ARG, "bad arguments");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
+  PoolScope pool(ctx);
   void *d_terms = nullptr, *d_rs = nullptr, *d_err = nullptr;
-  // (the blocks go back to the pool on every path)
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, &d_terms, std::max<size_t>(2 * (size_t)count * sizeof(double), 16)));
-    HIP_TRY(pool_malloc(ctx, &d_rs, sizeof(RateState)));
-    HIP_TRY(pool_malloc(ctx, &d_err, 16));
-    HIP_TRY(hipMemsetAsync(d_rs, 0, sizeof(RateState), st));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, st));
-    // (through the context's pinned buffers, as every entry: the runtime never pins the caller's pages)
-    if (count > 0)
-      HIP_TRY(h2d_user(ctx, d_terms, terms, 2 * (size_t)count * sizeof(double), st));
-    HIP_TRY(small_reset(ctx));
-    RateCtx cx{};
-    cx.tv.error = (int32_t*)d_err;
-    cx.n = count;
-    cx.a = 0;
-    cx.b = count;
-    cx.c = 1;
-    cx.term = (double*)d_terms;
-    cx.rs = (RateState*)d_rs;
-    hipLaunchKernelGGL(rate_sum_kernel, dim3(2), dim3(kAcSumThreads), 0, st, cx);
-    HIP_TRY(hipGetLastError());
-    void* p_rs = nullptr;
-    HIP_TRY(small_d2h(ctx, &p_rs, d_rs, sizeof(RateState), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const RateState& h = *(const RateState*)p_rs;
-    out[0] = h.bits[0];
-    out[1] = h.bits[1];
-    return GPCC_OK;
-  };
-  const int rc = run();
-  for (void* p : {d_terms, d_rs, d_err})
-    if (p)
-      pool_free(ctx, p);
-  return rc;
+  HIP_TRY(pool.take_bytes(std::max<size_t>(2 * (size_t)count * sizeof(double), 16), &d_terms));
+  HIP_TRY(pool.take_bytes(sizeof(RateState), &d_rs));
+  HIP_TRY(pool.take_bytes(16, &d_err));
+  HIP_TRY(hipMemsetAsync(d_rs, 0, sizeof(RateState), st));
+  HIP_TRY(hipMemsetAsync(d_err, 0, 16, st));
+  // (through the context's pinned buffers, as every entry: the runtime never pins the caller's pages)
+  if (count > 0)
+    HIP_TRY(h2d_user(ctx, d_terms, terms, 2 * (size_t)count * sizeof(double), st));
+  HIP_TRY(small_reset(ctx));
+  RateCtx cx{};
+  cx.tv.error = (int32_t*)d_err;
+  cx.n = count;
+  cx.a = 0;
+  cx.b = count;
+  cx.c = 1;
+  cx.term = (double*)d_terms;
+  cx.rs = (RateState*)d_rs;
+  hipLaunchKernelGGL(rate_sum_kernel, dim3(2), dim3(kAcSumThreads), 0, st, cx);
+  HIP_TRY(hipGetLastError());
+  void* p_rs = nullptr;
+  HIP_TRY(small_d2h(ctx, &p_rs, d_rs, sizeof(RateState), st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const RateState& h = *(const RateState*)p_rs;
+  out[0] = h.bits[0];
+  out[1] = h.bits[1];
+  return GPCC_OK;
 }
 
 // rdoq_threshold and rdoq_threshold_recip (raht_levels.hpp) alone, for tests/test_gpu_rdoq_edges.py: case i is
@@ -2856,13 +2882,14 @@ gpcc_debug_rdoq_threshold(
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t n = (size_t)count;
-  void *d_d = nullptr, *d_l = nullptr, *d_r = nullptr, *d_m = nullptr, *d_o = nullptr;
+  PoolScope pool(ctx);
   auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, &d_d, n * 8));
-    HIP_TRY(pool_malloc(ctx, &d_l, n * 8));
-    HIP_TRY(pool_malloc(ctx, &d_r, n * 4));
-    HIP_TRY(pool_malloc(ctx, &d_m, n * 4));
-    HIP_TRY(pool_malloc(ctx, &d_o, 2 * n * 4));
+    void *d_d = nullptr, *d_l = nullptr, *d_r = nullptr, *d_m = nullptr, *d_o = nullptr;
+    HIP_TRY(pool.take_bytes(n * 8, &d_d));
+    HIP_TRY(pool.take_bytes(n * 8, &d_l));
+    HIP_TRY(pool.take_bytes(n * 4, &d_r));
+    HIP_TRY(pool.take_bytes(n * 4, &d_m));
+    HIP_TRY(pool.take_bytes(2 * n * 4, &d_o));
     HIP_TRY(h2d_user(ctx, d_d, dist2, n * 8, st));
     HIP_TRY(h2d_user(ctx, d_l, lambda, n * 8, st));
     HIP_TRY(h2d_user(ctx, d_r, rate_coeff, n * 4, st));
@@ -2878,10 +2905,7 @@ gpcc_debug_rdoq_threshold(
   };
   const int rc = run();
   if (rc != GPCC_OK)
-    hipStreamSynchronize(st);  // (nothing reads the caller's arrays once the call has returned)
-  for (void* p : {d_d, d_l, d_r, d_m, d_o})
-    if (p)
-      pool_free(ctx, p);
+    hipStreamSynchronize(st);  // (nothing reads the caller's arrays, or a released block, once the call has returned)
   return rc;
 }
 
@@ -2907,20 +2931,21 @@ gpcc_debug_rdoq_resolve(
     return fail(GPCC_ERR_INVALID_ARG, "desc / coeffs is null");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  void *d_tab = nullptr, *d_sched = nullptr, *d_desc = nullptr, *d_co = nullptr, *d_state = nullptr, *d_misc = nullptr;
+  PoolScope pool(ctx);
   auto run = [&]() -> int {
+    void *d_tab = nullptr, *d_sched = nullptr, *d_desc = nullptr, *d_co = nullptr, *d_state = nullptr, *d_misc = nullptr;
     // tables: pt_off | tile_base | soff rows, each [s + 1]
     const size_t row = (size_t)s + 1, rows = 2 + (size_t)pl.nlev + 1;
     std::vector<int32_t> h_tab(rows * row);
     std::copy(pl.pt_off.begin(), pl.pt_off.end(), h_tab.begin());
     std::copy(pl.tile_base.begin(), pl.tile_base.end(), h_tab.begin() + row);
     std::copy(pl.soff.begin(), pl.soff.end(), h_tab.begin() + 2 * row);
-    HIP_TRY(pool_malloc(ctx, &d_tab, h_tab.size() * 4));
-    HIP_TRY(pool_malloc(ctx, &d_sched, (size_t)s * sizeof(SliceSched)));
-    HIP_TRY(pool_malloc(ctx, &d_desc, std::max<size_t>(n * 4, 16)));
-    HIP_TRY(pool_malloc(ctx, &d_co, std::max<size_t>(n * c * 4, 16)));
-    HIP_TRY(pool_malloc(ctx, &d_state, ((size_t)pl.num_tiles + 1) * sizeof(unsigned long long)));
-    HIP_TRY(pool_malloc(ctx, &d_misc, ((size_t)s + 4) * 4));  // error word (16 bytes), slice_l [s]
+    HIP_TRY(pool.take_bytes(h_tab.size() * 4, &d_tab));
+    HIP_TRY(pool.take_bytes((size_t)s * sizeof(SliceSched), &d_sched));
+    HIP_TRY(pool.take_bytes(std::max<size_t>(n * 4, 16), &d_desc));
+    HIP_TRY(pool.take_bytes(std::max<size_t>(n * c * 4, 16), &d_co));
+    HIP_TRY(pool.take_bytes(((size_t)pl.num_tiles + 1) * sizeof(unsigned long long), &d_state));
+    HIP_TRY(pool.take_bytes(((size_t)s + 4) * 4, &d_misc));  // error word (16 bytes), slice_l [s]
     HIP_TRY(h2d_user(ctx, d_tab, h_tab.data(), h_tab.size() * 4, st));
     HIP_TRY(h2d_user(ctx, d_sched, pl.sched.data(), (size_t)s * sizeof(SliceSched), st));
     if (n > 0) {
@@ -2968,10 +2993,7 @@ gpcc_debug_rdoq_resolve(
   };
   const int rc = run();
   if (rc != GPCC_OK)
-    hipStreamSynchronize(st);  // (nothing reads the call's host tables once it has returned)
-  for (void* p : {d_tab, d_sched, d_desc, d_co, d_state, d_misc})
-    if (p)
-      pool_free(ctx, p);
+    hipStreamSynchronize(st);  // (nothing reads the call's host tables, or a released block, once it has returned)
   return rc;
 }
 
@@ -2987,8 +3009,9 @@ gpcc_debug_guard_selftest(gpcc_ctx* ctx, int mode)
   if (!guard_mode())  // (without the bands the write below would leave the allocation: nothing to test)
     return GPCC_OK;
   if (mode == 0) {
+    PoolScope pool(ctx);  // (released, and so compared, at the end of this block)
     void* p = nullptr;
-    HIP_TRY(pool_malloc(ctx, &p, 1024));
+    HIP_TRY(pool.take_bytes(1024, &p));
     // (the pool rounds a request up by an eighth: the band starts behind the block's capacity)
     size_t cap = 0;
     for (auto& b : ctx->pool)
@@ -2996,7 +3019,6 @@ gpcc_debug_guard_selftest(gpcc_ctx* ctx, int mode)
         cap = b.cap;
     cap = (cap + 255) & ~size_t(255);
     HIP_TRY(hipMemsetAsync((char*)p + cap, 0, 16, ctx->stream));
-    pool_free(ctx, p);
   } else {
     int r = ensure_arena(ctx, 1 << 16);
     if (r)
@@ -3133,17 +3155,15 @@ gpcc_ctx_reserve(gpcc_ctx* ctx, int64_t max_points, int32_t max_slices, int32_t 
     // the host tier's device buffers for a slice of max_points points (host_transform): Morton codes,
     // attributes, coefficients, region QP offsets -- into the pool, where the calls find them
     const size_t n = (size_t)max_points;
+    PoolScope pool(ctx);
     void* blk[4] = {nullptr, nullptr, nullptr, nullptr};
     const size_t sz[4] = {8 * n, 4 * n * (size_t)max_c, 4 * n * (size_t)max_c, 8 * n};
     for (int i = 0; i < 4; i++)
-      if (pool_malloc(ctx, &blk[i], sz[i]) != hipSuccess)
+      if (pool.take_bytes(sz[i], &blk[i]) != hipSuccess)
         blk[i] = nullptr;
     for (int i = 0; i < 4; i++)
-      if (blk[i]) {
-        if (touch)
-          hipMemsetAsync(blk[i], 0, sz[i], ctx->stream);
-        pool_free(ctx, blk[i]);
-      }
+      if (blk[i] && touch)
+        hipMemsetAsync(blk[i], 0, sz[i], ctx->stream);
   }
   // pinned staging of the level kernels and of the compact level pass (launch_transform / launch_cx)
   const size_t stage_bytes = sizeof(gpcc_raht_params) + 2 * ((size_t)max_slices + 1) * sizeof(int32_t)
@@ -3351,6 +3371,19 @@ dev_morton_sort(
   return GPCC_OK;
 }
 
+// the largest coordinate of n positions in host memory; one outside what a Morton code holds is refused
+static int
+max_coordinate(const int32_t* xyz, int64_t n, int32_t* mx, const char* refusal = "coordinate outside [0, 2^21)")
+{
+  *mx = 0;
+  for (int64_t i = 0; i < n * 3; i++) {
+    if (xyz[i] < 0 || xyz[i] >= (1 << 21))
+      return fail(GPCC_ERR_INVALID_ARG, refusal);
+    *mx = std::max(*mx, xyz[i]);
+  }
+  return GPCC_OK;
+}
+
 static int
 host_morton_sort(
   gpcc_ctx* ctx, const int32_t* xyz, int32_t n, int64_t* morton, int32_t* order)
@@ -3362,41 +3395,31 @@ host_morton_sort(
   if (n > kMaxPoints)
     return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per call");
   int32_t mx = 0;
-  for (int64_t i = 0; i < (int64_t)n * 3; i++) {
-    if (xyz[i] < 0 || xyz[i] >= (1 << 21))
-      return fail(GPCC_ERR_INVALID_ARG, "coordinate outside [0, 2^21)");
-    mx = std::max(mx, xyz[i]);
-  }
+  int r = max_coordinate(xyz, n, &mx);
+  if (r)
+    return r;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
+  const size_t N = (size_t)n;
+  PoolScope pool(ctx);
   int32_t* d_x = nullptr;
   int64_t* d_m = nullptr;
   int32_t* d_o = nullptr;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_x);
-    pool_free(ctx, d_m);
-    pool_free(ctx, d_o);
-  };
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_x, sizeof(int32_t) * 3 * n));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_m, sizeof(int64_t) * n));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_o, sizeof(int32_t) * n));
-    HIP_TRY(h2d_user(ctx, d_x, xyz, sizeof(int32_t) * 3 * n, st));
-    const int saved = ctx->morton_bits;
-    ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)mx));
-    const int64_t offs[2] = {0, n};
-    int r = dev_morton_sort(ctx, 1, offs, d_x, d_m, d_o);
-    ctx->morton_bits = saved;
-    if (r)
-      return r;
-    HIP_TRY(d2h_user(ctx, morton, d_m, sizeof(int64_t) * n, st));
-    HIP_TRY(d2h_user(ctx, order, d_o, sizeof(int32_t) * n, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return GPCC_OK;
-  };
-  int r = run();
-  cleanup();
-  return r;
+  HIP_TRY(pool.take(3 * N, &d_x));
+  HIP_TRY(pool.take(N, &d_m));
+  HIP_TRY(pool.take(N, &d_o));
+  HIP_TRY(h2d_user(ctx, d_x, xyz, sizeof(int32_t) * 3 * n, st));
+  const int saved = ctx->morton_bits;
+  ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)mx));
+  const int64_t offs[2] = {0, n};
+  r = dev_morton_sort(ctx, 1, offs, d_x, d_m, d_o);
+  ctx->morton_bits = saved;
+  if (r)
+    return r;
+  HIP_TRY(d2h_user(ctx, morton, d_m, sizeof(int64_t) * n, st));
+  HIP_TRY(d2h_user(ctx, order, d_o, sizeof(int32_t) * n, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GPCC_OK;
 }
 
 static int
@@ -3517,9 +3540,12 @@ lod_build_core(
       return fail(
         GPCC_ERR_UNSUPPORTED,
         "inter prediction together with scalable lifting / canonical point order stays on the reference CPU path");
-    for (int64_t i = 0; !frame->on_device && i < (int64_t)frame->n * 3; i++)
-      if (frame->xyz[i] < 0 || frame->xyz[i] >= (1 << 21))
-        return fail(GPCC_ERR_INVALID_ARG, "reference frame coordinate outside [0, 2^21)");
+    int32_t frame_mx = 0;
+    if (!frame->on_device) {
+      int rf = max_coordinate(frame->xyz, frame->n, &frame_mx, "reference frame coordinate outside [0, 2^21)");
+      if (rf)
+        return rf;
+    }
   }
   const bool scalable = lp->scalable_lifting_enabled_flag != 0;
   if (!scalable && (lp->lod_decimation_type < 0 || lp->lod_decimation_type > 2))
@@ -3536,11 +3562,9 @@ lod_build_core(
     // hint bounds the sort's passes (gpcc_ctx_set_morton_bits, 0 = all 63)
     mx = ctx->morton_bits > 0 ? (1 << std::min(21, (ctx->morton_bits + 2) / 3)) - 1 : (1 << 21) - 1;
   } else {
-    for (int64_t i = 0; i < (int64_t)n * 3; i++) {
-      if (xyz[i] < 0 || xyz[i] >= (1 << 21))
-        return fail(GPCC_ERR_INVALID_ARG, "coordinate outside [0, 2^21)");
-      mx = std::max(mx, xyz[i]);
-    }
+    int rx = max_coordinate(xyz, n, &mx);
+    if (rx)
+      return rx;
   }
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -4263,15 +4287,9 @@ rdo_attr_driver(
   hipStream_t st = ctx->stream;
   const size_t N = (size_t)n;
   // what outlives a candidate's workspace (the arena is laid out again by the second build)
+  PoolScope pool(ctx);
   int32_t *d_xyz = nullptr, *d_orig = nullptr, *d_rec[2] = {nullptr, nullptr};
   unsigned long long* d_dist = nullptr;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_dist);
-    pool_free(ctx, d_rec[1]);
-    pool_free(ctx, d_rec[0]);
-    pool_free(ctx, d_orig);
-    pool_free(ctx, d_xyz);
-  };
   const typename Coder::Frame frame = Coder::stage_frame(attrs_ref, (size_t)n_ref);
   auto candidate = [&](int k) -> int {
     const bool inter = k == 0;
@@ -4302,45 +4320,40 @@ rdo_attr_driver(
         return GPCC_OK;
       });
   };
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_orig, sizeof(int32_t) * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_rec[0], sizeof(int32_t) * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_rec[1], sizeof(int32_t) * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_dist, 2 * sizeof(unsigned long long)));
-    HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
-    HIP_TRY(h2d_user(ctx, d_orig, attrs, sizeof(int32_t) * N, st));
-    for (int k = 0; k < 2; k++) {
-      int r = candidate(k);
-      if (r)
-        return r;
-    }
-    HIP_TRY(hipMemsetAsync(d_dist, 0, 2 * sizeof(unsigned long long), st));
-    {
-      Timer tm(ctx, "slice_distortion");
-      SliceDistArgs a{};
-      a.rec[0] = d_rec[0];
-      a.rec[1] = d_rec[1];
-      a.orig = d_orig;
-      a.out = d_dist;
-      a.n = n;
-      a.num = 2;
-      hipLaunchKernelGGL(
-        slice_distortion_kernel, dim3(slice_distortion_grid(n)), dim3(kSliceDistBlock), 0, st, a);
-    }
-    HIP_TRY(hipGetLastError());
-    unsigned long long h_dist[2] = {0, 0};
-    HIP_TRY(d2h_user(ctx, recon, d_rec[0], sizeof(int32_t) * N, st));
-    HIP_TRY(d2h_user(ctx, recon + N, d_rec[1], sizeof(int32_t) * N, st));
-    HIP_TRY(hipMemcpyAsync(h_dist, d_dist, sizeof(h_dist), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    dist[0] = (int64_t)h_dist[0];
-    dist[1] = (int64_t)h_dist[1];
-    return GPCC_OK;
-  };
-  int r = run();
-  cleanup();
-  return r;
+  HIP_TRY(pool.take(3 * N, &d_xyz));
+  HIP_TRY(pool.take(N, &d_orig));
+  HIP_TRY(pool.take(N, &d_rec[0]));
+  HIP_TRY(pool.take(N, &d_rec[1]));
+  HIP_TRY(pool.take(2, &d_dist));
+  HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
+  HIP_TRY(h2d_user(ctx, d_orig, attrs, sizeof(int32_t) * N, st));
+  for (int k = 0; k < 2; k++) {
+    int r = candidate(k);
+    if (r)
+      return r;
+  }
+  HIP_TRY(hipMemsetAsync(d_dist, 0, 2 * sizeof(unsigned long long), st));
+  {
+    Timer tm(ctx, "slice_distortion");
+    SliceDistArgs a{};
+    a.rec[0] = d_rec[0];
+    a.rec[1] = d_rec[1];
+    a.orig = d_orig;
+    a.out = d_dist;
+    a.n = n;
+    a.num = 2;
+    hipLaunchKernelGGL(
+      slice_distortion_kernel, dim3(slice_distortion_grid(n)), dim3(kSliceDistBlock), 0, st, a);
+  }
+  HIP_TRY(hipGetLastError());
+  unsigned long long h_dist[2] = {0, 0};
+  HIP_TRY(d2h_user(ctx, recon, d_rec[0], sizeof(int32_t) * N, st));
+  HIP_TRY(d2h_user(ctx, recon + N, d_rec[1], sizeof(int32_t) * N, st));
+  HIP_TRY(hipMemcpyAsync(h_dist, d_dist, sizeof(h_dist), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  dist[0] = (int64_t)h_dist[0];
+  dist[1] = (int64_t)h_dist[1];
+  return GPCC_OK;
 }
 
 // ---- a slice with attribute inter prediction in one call -------------------------------------------
@@ -4422,6 +4435,50 @@ inter_attr_driver(
   return GPCC_OK;
 }
 
+// ---- zero-run formation where the coefficients are (symbol_stream.hpp): only symbols cross PCIe ----
+struct ZeroRunWork {
+  int32_t *pos, *nz, *runs, *vals, *small;
+  uint8_t* flags;
+  unsigned long long* scan;
+};
+
+// (with ar.base == nullptr this only measures)
+void
+zero_run_carve(Arena& ar, ZeroRunWork& w, size_t N, int c)
+{
+  w.pos = ar.take<int32_t>(N);
+  w.nz = ar.take<int32_t>(N + 1);  // non-zero positions
+  w.runs = ar.take<int32_t>(N);
+  w.vals = ar.take<int32_t>(N * c);
+  w.flags = ar.take<uint8_t>(N);
+  w.small = ar.take<int32_t>(64);
+  w.scan = ar.take<unsigned long long>(1024);
+}
+
+// d_co [n][c] on the device (planar: [c][n]) to (zero run, values) symbols in w.runs / w.vals, for the caller to
+// download; the one host wait leaves their number and the trailing run in h
+int
+zero_run_pack_on_device(
+  gpcc_ctx* ctx, const int32_t* d_co, int32_t n, int32_t c, int32_t planar, const ZeroRunWork& w, int32_t h[2])
+{
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemsetAsync(w.small, 0, sizeof(int32_t) * 64, st));
+  HIP_TRY(hipMemsetAsync(w.scan, 0, sizeof(unsigned long long) * 1024, st));
+  {
+    Timer tm(ctx, "zero_run_pack");
+    zero_run_flags_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, c, planar, d_co, w.flags, w.pos);
+    const int grid = (int)std::min<int64_t>(1024, ((int64_t)n + 1023) / 1024);
+    lod_partition_kernel<<<std::max(grid, 1), 256, 0, st>>>(
+      n, w.flags, w.pos, w.nz, nullptr, w.small, w.scan, 1);
+    zero_run_emit_kernel<<<grid_for(n, 256), 256, 0, st>>>(
+      n, c, planar, d_co, w.nz, w.small, w.runs, w.vals, w.small + 1);
+  }
+  h[0] = h[1] = 0;
+  HIP_TRY(hipMemcpyAsync(h, w.small, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GPCC_OK;
+}
+
 int
 slice_driver(
   gpcc_ctx* ctx, const gpcc_raht_params* params, bool encoder, const int32_t* xyz,
@@ -4443,134 +4500,94 @@ slice_driver(
   if (rcode)
     return rcode;
   int32_t mx = 0;
-  for (int64_t i = 0; i < (int64_t)n * 3; i++) {
-    if (xyz[i] < 0 || xyz[i] >= (1 << 21))
-      return fail(GPCC_ERR_INVALID_ARG, "coordinate outside [0, 2^21)");
-    mx = std::max(mx, xyz[i]);
-  }
+  rcode = max_coordinate(xyz, n, &mx);
+  if (rcode)
+    return rcode;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t N = (size_t)n;
+  PoolScope pool(ctx);
   int32_t *d_xyz = nullptr, *d_order = nullptr, *d_pt = nullptr, *d_a = nullptr, *d_c = nullptr;
-  int32_t *d_qu = nullptr, *d_q = nullptr;  // QP-region offsets per point: input order, Morton order
   int64_t* d_m = nullptr;
-  char* d_pack = nullptr;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_pack);
-    pool_free(ctx, d_qu);
-    pool_free(ctx, d_q);
-    pool_free(ctx, d_xyz);
-    pool_free(ctx, d_order);
-    pool_free(ctx, d_pt);
-    pool_free(ctx, d_a);
-    pool_free(ctx, d_c);
-    pool_free(ctx, d_m);
-  };
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_order, sizeof(int32_t) * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_m, sizeof(int64_t) * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_pt, sizeof(int32_t) * N * c));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_a, sizeof(int32_t) * N * c));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_c, sizeof(int32_t) * N * c));
-    HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
-    const int bits = std::max(1, 3 * bitlen64((uint64_t)mx));
-    const int64_t offs[2] = {0, n};
-    {
-      const int saved = ctx->morton_bits;
-      ctx->morton_bits = bits;
-      int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_m, d_order);
-      ctx->morton_bits = saved;
-      if (r)
-        return r;
-    }
-    if (encoder) {
-      HIP_TRY(h2d_user(ctx, d_pt, attrs, sizeof(int32_t) * N * c, st));
-      {
-        Timer tm(ctx, "attr_gather");
-        attr_gather_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, c, d_order, d_pt, d_a);
-      }
-      HIP_TRY(hipMemsetAsync(d_c, 0, sizeof(int32_t) * N * c, st));
-    } else {
-      HIP_TRY(h2d_user(ctx, d_c, coeffs, sizeof(int32_t) * N * c, st));
-    }
-    // QP regions: the offset of the first box that holds the point (qpSet.regionQpOffset), in the order of
-    // the Morton codes like the attributes
-    const int32_t* d_qp = nullptr;
-    if (regions && regions->num_qp_regions != 0) {
-      HIP_TRY(pool_malloc(ctx, (void**)&d_qu, sizeof(int32_t) * 2 * N));
-      HIP_TRY(pool_malloc(ctx, (void**)&d_q, sizeof(int32_t) * 2 * N));
-      const int32_t* filled = nullptr;
-      int rq = qp_regions_to_points(regions, d_xyz, n, d_qu, st, &filled);
-      if (rq)
-        return rq;
-      attr_gather_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, 2, d_order, d_qu, d_q);
-      d_qp = d_q;
-    }
-    int r = dev_transform(ctx, params, encoder, 1, offs, d_m, d_qp, d_a, d_c, c, bits);
+  HIP_TRY(pool.take(3 * N, &d_xyz));
+  HIP_TRY(pool.take(N, &d_order));
+  HIP_TRY(pool.take(N, &d_m));
+  HIP_TRY(pool.take(N * c, &d_pt));
+  HIP_TRY(pool.take(N * c, &d_a));
+  HIP_TRY(pool.take(N * c, &d_c));
+  HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
+  const int bits = std::max(1, 3 * bitlen64((uint64_t)mx));
+  const int64_t offs[2] = {0, n};
+  {
+    const int saved = ctx->morton_bits;
+    ctx->morton_bits = bits;
+    int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_m, d_order);
+    ctx->morton_bits = saved;
     if (r)
       return r;
+  }
+  if (encoder) {
+    HIP_TRY(h2d_user(ctx, d_pt, attrs, sizeof(int32_t) * N * c, st));
     {
-      Timer tm(ctx, "attr_clip_scatter");
-      attr_clip_scatter_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-        n, c, (1 << bitdepth) - 1, d_order, d_a, d_pt);
+      Timer tm(ctx, "attr_gather");
+      attr_gather_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, c, d_order, d_pt, d_a);
     }
-    if (packed) {
-      // zero-run formation where the coefficients are: only symbols cross PCIe
-      Arena ar;
-      ar.take<int32_t>(N);          // positions
-      ar.take<int32_t>(N + 1);      // non-zero positions
-      ar.take<int32_t>(N);          // runs
-      ar.take<int32_t>(N * c);      // values
-      ar.take<uint8_t>(N);          // flags
-      ar.take<int32_t>(64);
-      ar.take<unsigned long long>(1024);
-      HIP_TRY(pool_malloc(ctx, (void**)&d_pack, ar.used));
-      ar.base = d_pack;
-      ar.reset();
-      int32_t* d_pos = ar.take<int32_t>(N);
-      int32_t* d_nz = ar.take<int32_t>(N + 1);
-      int32_t* d_runs = ar.take<int32_t>(N);
-      int32_t* d_vals = ar.take<int32_t>(N * c);
-      uint8_t* d_flags = ar.take<uint8_t>(N);
-      int32_t* d_small = ar.take<int32_t>(64);
-      unsigned long long* d_scan = ar.take<unsigned long long>(1024);
-      HIP_TRY(hipMemsetAsync(d_small, 0, sizeof(int32_t) * 64, st));
-      HIP_TRY(hipMemsetAsync(d_scan, 0, sizeof(unsigned long long) * 1024, st));
-      {
-        Timer tm(ctx, "zero_run_pack");
-        zero_run_flags_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, c, 1, d_c, d_flags, d_pos);
-        const int grid = (int)std::min<int64_t>(1024, ((int64_t)n + 1023) / 1024);
-        lod_partition_kernel<<<std::max(grid, 1), 256, 0, st>>>(
-          n, d_flags, d_pos, d_nz, nullptr, d_small, d_scan, 1);
-        zero_run_emit_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-          n, c, 1, d_c, d_nz, d_small, d_runs, d_vals, d_small + 1);
-      }
-      int32_t h[2] = {0, 0};
-      HIP_TRY(hipMemcpyAsync(h, d_small, sizeof(h), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (h[0] > 0) {
-        HIP_TRY(d2h_user(ctx, runs, d_runs, sizeof(int32_t) * (size_t)h[0], st));
-        HIP_TRY(d2h_user(ctx, values, d_vals, sizeof(int32_t) * (size_t)h[0] * c, st));
-      }
-      *num_symbols = h[0];
-      *trailing_run = h[1];
-    }
-    // the caller's attributes are overwritten only after the device result is
-    // known to be valid (on failure they still hold the source)
-    HIP_TRY(hipStreamSynchronize(st));
-    r = check_device_error(ctx);
+    HIP_TRY(hipMemsetAsync(d_c, 0, sizeof(int32_t) * N * c, st));
+  } else {
+    HIP_TRY(h2d_user(ctx, d_c, coeffs, sizeof(int32_t) * N * c, st));
+  }
+  // QP regions: the offset of the first box that holds the point (qpSet.regionQpOffset), in the order of
+  // the Morton codes like the attributes
+  const int32_t* d_qp = nullptr;
+  if (regions && regions->num_qp_regions != 0) {
+    int32_t *d_qu = nullptr, *d_q = nullptr;  // the offsets per point: input order, Morton order
+    HIP_TRY(pool.take(2 * N, &d_qu));
+    HIP_TRY(pool.take(2 * N, &d_q));
+    const int32_t* filled = nullptr;
+    int rq = qp_regions_to_points(regions, d_xyz, n, d_qu, st, &filled);
+    if (rq)
+      return rq;
+    attr_gather_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, 2, d_order, d_qu, d_q);
+    d_qp = d_q;
+  }
+  int r = dev_transform(ctx, params, encoder, 1, offs, d_m, d_qp, d_a, d_c, c, bits);
+  if (r)
+    return r;
+  {
+    Timer tm(ctx, "attr_clip_scatter");
+    attr_clip_scatter_kernel<<<grid_for(n, 256), 256, 0, st>>>(
+      n, c, (1 << bitdepth) - 1, d_order, d_a, d_pt);
+  }
+  if (packed) {
+    // the symbols instead of the coefficients: the pack's workspace is a block of the pool
+    Arena ar;
+    ZeroRunWork w;
+    zero_run_carve(ar, w, N, c);
+    HIP_TRY(pool.take(ar.used, &ar.base));
+    ar.reset();
+    zero_run_carve(ar, w, N, c);
+    int32_t h[2];
+    r = zero_run_pack_on_device(ctx, d_c, n, c, 1, w, h);
     if (r)
       return r;
-    HIP_TRY(d2h_user(ctx, attrs, d_pt, sizeof(int32_t) * N * c, st));
-    if (encoder && !packed)
-      HIP_TRY(d2h_user(ctx, coeffs, d_c, sizeof(int32_t) * N * c, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return GPCC_OK;
-  };
-  int r = run();
-  cleanup();
-  return r;
+    if (h[0] > 0) {
+      HIP_TRY(d2h_user(ctx, runs, w.runs, sizeof(int32_t) * (size_t)h[0], st));
+      HIP_TRY(d2h_user(ctx, values, w.vals, sizeof(int32_t) * (size_t)h[0] * c, st));
+    }
+    *num_symbols = h[0];
+    *trailing_run = h[1];
+  }
+  // the caller's attributes are overwritten only after the device result is
+  // known to be valid (on failure they still hold the source)
+  HIP_TRY(hipStreamSynchronize(st));
+  r = check_device_error(ctx);
+  if (r)
+    return r;
+  HIP_TRY(d2h_user(ctx, attrs, d_pt, sizeof(int32_t) * N * c, st));
+  if (encoder && !packed)
+    HIP_TRY(d2h_user(ctx, coeffs, d_c, sizeof(int32_t) * N * c, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GPCC_OK;
 }
 
 int
@@ -4588,19 +4605,12 @@ zero_run_pack(
   hipStream_t st = ctx->stream;
   const size_t N = (size_t)n;
   Arena m;
-  int32_t *d_co, *d_pos, *d_nz, *d_runs, *d_vals, *d_small;
-  uint8_t* d_flags;
-  unsigned long long* d_scan;
+  int32_t* d_co;
+  ZeroRunWork w;
   auto carve = [&](Arena& ar) {
     ar.reset();
     d_co = ar.take<int32_t>(N * c);
-    d_pos = ar.take<int32_t>(N);
-    d_nz = ar.take<int32_t>(N + 1);
-    d_runs = ar.take<int32_t>(N);
-    d_vals = ar.take<int32_t>(N * c);
-    d_flags = ar.take<uint8_t>(N);
-    d_small = ar.take<int32_t>(64);
-    d_scan = ar.take<unsigned long long>(1024);
+    zero_run_carve(ar, w, N, c);
   };
   carve(m);
   int rcode = ensure_arena(ctx, m.used);
@@ -4608,24 +4618,13 @@ zero_run_pack(
     return rcode;
   carve(ctx->arena);
   HIP_TRY(h2d_user(ctx, d_co, coeffs, sizeof(int32_t) * N * c, st));
-  HIP_TRY(hipMemsetAsync(d_small, 0, sizeof(int32_t) * 64, st));
-  HIP_TRY(hipMemsetAsync(d_scan, 0, sizeof(unsigned long long) * 1024, st));
-  {
-    Timer tm(ctx, "zero_run_pack");
-    zero_run_flags_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, c, planar, d_co, d_flags, d_pos);
-    const int grid = (int)std::min<int64_t>(1024, ((int64_t)n + 1023) / 1024);
-    lod_partition_kernel<<<std::max(grid, 1), 256, 0, st>>>(
-      n, d_flags, d_pos, d_nz, nullptr, d_small, d_scan, 1);
-    zero_run_emit_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-      n, c, planar, d_co, d_nz, d_small, d_runs, d_vals, d_small + 1);
-  }
-  int32_t h[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(h, d_small, sizeof(h), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  // only the symbols cross PCIe
+  int32_t h[2];
+  rcode = zero_run_pack_on_device(ctx, d_co, n, c, planar, w, h);
+  if (rcode)
+    return rcode;
   if (h[0] > 0) {
-    HIP_TRY(d2h_user(ctx, runs, d_runs, sizeof(int32_t) * (size_t)h[0], st));
-    HIP_TRY(d2h_user(ctx, values, d_vals, sizeof(int32_t) * (size_t)h[0] * c, st));
+    HIP_TRY(d2h_user(ctx, runs, w.runs, sizeof(int32_t) * (size_t)h[0], st));
+    HIP_TRY(d2h_user(ctx, values, w.vals, sizeof(int32_t) * (size_t)h[0] * c, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   *num_symbols = h[0];
@@ -4651,42 +4650,33 @@ estimate_dist2(
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int ns = (n + sampling_period - 1) / sampling_period;
+  PoolScope pool(ctx);
   int32_t* d_xyz = nullptr;
   long long* d_dist = nullptr;
   std::vector<long long> dists((size_t)ns);
-  int rc = GPCC_OK;
-  do {
-    if (pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * (size_t)n) != hipSuccess
-        || pool_malloc(ctx, (void**)&d_dist, sizeof(long long) * (size_t)ns) != hipSuccess) {
-      rc = fail(GPCC_ERR_OUT_OF_MEMORY, "hipMalloc(estimate_dist2)");
-      break;
-    }
-    hipError_t e = h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * (size_t)n, st);
-    if (e == hipSuccess) {
-      Timer tm(ctx, "estimate_dist2");
-      estimate_dist2_kernel<<<grid_for(ns * 64, 256), 256, 0, st>>>(
-        n, d_xyz, sampling_period, search_range, ns, d_dist);
-    }
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(dists.data(), d_dist, sizeof(long long) * (size_t)ns, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-      rc = fail(GPCC_ERR_HIP, hipGetErrorString(e));
-      break;
-    }
-    // int p = int(std::floor(dists.size() * percentileEstimate)), :1712
-    const int p = int(std::floor(dists.size() * percentile));
-    std::nth_element(dists.begin(), dists.begin() + p, dists.end());
-    const long long dist2 = dists[p];
-    int shift = 0;
-    while ((int64_t(3) << (shift << 1)) < dist2 && shift < 20)
-      ++shift;
-    *shift_bits = shift;
-  } while (0);
-  pool_free(ctx, d_xyz);
-  pool_free(ctx, d_dist);
-  return rc;
+  if (pool.take(3 * (size_t)n, &d_xyz) != hipSuccess || pool.take((size_t)ns, &d_dist) != hipSuccess)
+    return fail(GPCC_ERR_OUT_OF_MEMORY, "hipMalloc(estimate_dist2)");
+  hipError_t e = h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * (size_t)n, st);
+  if (e == hipSuccess) {
+    Timer tm(ctx, "estimate_dist2");
+    estimate_dist2_kernel<<<grid_for(ns * 64, 256), 256, 0, st>>>(
+      n, d_xyz, sampling_period, search_range, ns, d_dist);
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dists.data(), d_dist, sizeof(long long) * (size_t)ns, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  if (e != hipSuccess)
+    return fail(GPCC_ERR_HIP, hipGetErrorString(e));
+  // int p = int(std::floor(dists.size() * percentileEstimate)), :1712
+  const int p = int(std::floor(dists.size() * percentile));
+  std::nth_element(dists.begin(), dists.begin() + p, dists.end());
+  const long long dist2 = dists[p];
+  int shift = 0;
+  while ((int64_t(3) << (shift << 1)) < dist2 && shift < 20)
+    ++shift;
+  *shift_bits = shift;
+  return GPCC_OK;
 }
 
 }  // namespace
@@ -5435,33 +5425,28 @@ host_to_spherical(
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
+  PoolScope pool(ctx);
   int32_t* d_pos = nullptr;
   int32_t* d_box = nullptr;
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_pos, sizeof(int32_t) * 3 * n));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_box, sizeof(int32_t) * 6));
-    HIP_TRY(h2d_user(ctx, d_pos, xyz, sizeof(int32_t) * 3 * n, st));
-    const int64_t offs[2] = {0, n};
-    int r = dev_to_spherical(ctx, sp, 1, offs, d_pos, d_pos, d_box);
-    if (r)
-      return r;
-    HIP_TRY(small_reset(ctx));
-    int32_t* h_box = (int32_t*)small_slot(ctx, sizeof(int32_t) * 6);
-    HIP_TRY(hipMemcpyAsync(h_box, d_box, sizeof(int32_t) * 6, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    r = check_device_error(ctx);
-    if (r)
-      return r;
-    HIP_TRY(d2h_user(ctx, pos_out, d_pos, sizeof(int32_t) * 3 * n, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bbox)
-      memcpy(bbox, h_box, sizeof(int32_t) * 6);
-    return GPCC_OK;
-  };
-  r = run();
-  pool_free(ctx, d_pos);
-  pool_free(ctx, d_box);
-  return r;
+  HIP_TRY(pool.take(3 * (size_t)n, &d_pos));
+  HIP_TRY(pool.take(6, &d_box));
+  HIP_TRY(h2d_user(ctx, d_pos, xyz, sizeof(int32_t) * 3 * n, st));
+  const int64_t offs[2] = {0, n};
+  r = dev_to_spherical(ctx, sp, 1, offs, d_pos, d_pos, d_box);
+  if (r)
+    return r;
+  HIP_TRY(small_reset(ctx));
+  int32_t* h_box = (int32_t*)small_slot(ctx, sizeof(int32_t) * 6);
+  HIP_TRY(hipMemcpyAsync(h_box, d_box, sizeof(int32_t) * 6, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  r = check_device_error(ctx);
+  if (r)
+    return r;
+  HIP_TRY(d2h_user(ctx, pos_out, d_pos, sizeof(int32_t) * 3 * n, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (bbox)
+    memcpy(bbox, h_box, sizeof(int32_t) * 6);
+  return GPCC_OK;
 }
 
 }  // namespace
@@ -5643,42 +5628,34 @@ host_ref_crop(
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t N = (size_t)n, NF = (size_t)n_frame, cap = std::min((size_t)capacity, NF);
+  PoolScope pool(ctx);
   int32_t *d_xyz = nullptr, *d_fx = nullptr, *d_fa = nullptr, *d_ox = nullptr, *d_oa = nullptr;
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_xyz, sizeof(int32_t) * 3 * N));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_fx, sizeof(int32_t) * 3 * NF));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_fa, sizeof(int32_t) * c * NF));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_ox, sizeof(int32_t) * 3 * std::max<size_t>(cap, 1)));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_oa, sizeof(int32_t) * c * std::max<size_t>(cap, 1)));
-    HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
-    HIP_TRY(h2d_user(ctx, d_fx, xyz_frame, sizeof(int32_t) * 3 * NF, st));
-    HIP_TRY(h2d_user(ctx, d_fa, attrs_frame, sizeof(int32_t) * c * NF, st));
-    const int64_t offs[2] = {0, n};
-    int64_t ro[2] = {0, -1};
-    int32_t box[6];
-    // (a crop never keeps more than the frame has: a larger capacity needs no larger buffer)
-    int r = dev_ref_crop(ctx, 1, offs, d_xyz, n_frame, d_fx, d_fa, c, d_ox, d_oa, (int64_t)cap, ro, box);
-    if (ro[1] >= 0)
-      *n_ref = (int32_t)ro[1];
-    if (r)
-      return r;
-    const size_t kept = (size_t)ro[1];
-    if (kept) {
-      HIP_TRY(d2h_user(ctx, xyz_ref, d_ox, sizeof(int32_t) * 3 * kept, st));
-      HIP_TRY(d2h_user(ctx, attrs_ref, d_oa, sizeof(int32_t) * c * kept, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bbox)
-      memcpy(bbox, box, sizeof(box));
-    return GPCC_OK;
-  };
-  r = run();
-  pool_free(ctx, d_oa);
-  pool_free(ctx, d_ox);
-  pool_free(ctx, d_fa);
-  pool_free(ctx, d_fx);
-  pool_free(ctx, d_xyz);
-  return r;
+  HIP_TRY(pool.take(3 * N, &d_xyz));
+  HIP_TRY(pool.take(3 * NF, &d_fx));
+  HIP_TRY(pool.take(c * NF, &d_fa));
+  HIP_TRY(pool.take(3 * std::max<size_t>(cap, 1), &d_ox));
+  HIP_TRY(pool.take(c * std::max<size_t>(cap, 1), &d_oa));
+  HIP_TRY(h2d_user(ctx, d_xyz, xyz, sizeof(int32_t) * 3 * N, st));
+  HIP_TRY(h2d_user(ctx, d_fx, xyz_frame, sizeof(int32_t) * 3 * NF, st));
+  HIP_TRY(h2d_user(ctx, d_fa, attrs_frame, sizeof(int32_t) * c * NF, st));
+  const int64_t offs[2] = {0, n};
+  int64_t ro[2] = {0, -1};
+  int32_t box[6];
+  // (a crop never keeps more than the frame has: a larger capacity needs no larger buffer)
+  r = dev_ref_crop(ctx, 1, offs, d_xyz, n_frame, d_fx, d_fa, c, d_ox, d_oa, (int64_t)cap, ro, box);
+  if (ro[1] >= 0)
+    *n_ref = (int32_t)ro[1];
+  if (r)
+    return r;
+  const size_t kept = (size_t)ro[1];
+  if (kept) {
+    HIP_TRY(d2h_user(ctx, xyz_ref, d_ox, sizeof(int32_t) * 3 * kept, st));
+    HIP_TRY(d2h_user(ctx, attrs_ref, d_oa, sizeof(int32_t) * c * kept, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  if (bbox)
+    memcpy(bbox, box, sizeof(box));
+  return GPCC_OK;
 }
 
 }  // namespace
@@ -5776,43 +5753,39 @@ host_quantize_positions(
   a.error = ctx->d_error;
 
   const size_t N = (size_t)n;
+  PoolScope pool(ctx);
   int32_t* d_src = nullptr;
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_src, sizeof(int32_t) * 3 * N));
-    HIP_TRY(h2d_user(ctx, d_src, src_xyz, sizeof(int32_t) * 3 * N, st));
-    a.src = d_src;
-    auto span = [&](const char* name) { return Timer(ctx, name); };
-    HIP_TRY(qz_count_launch(st, a, w, max1, max2, span));
-    // the one host wait: the number of destination points and the error word
-    HIP_TRY(small_reset(ctx));
-    int32_t* h_count = (int32_t*)small_slot(ctx, sizeof(int32_t));
-    if (!h_count)
-      return fail(GPCC_ERR_HIP, "no pinned slot");
-    *h_count = n;
-    if (p->mode != 0)
-      HIP_TRY(hipMemcpyAsync(h_count, w.counts + w.num_tiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (ctx->h_error)
-      HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    int r = check_device_error(ctx);
-    if (r)
-      return r;
-    const size_t kept = (size_t)*h_count;
-    if (p->mode == 0) {
-      HIP_TRY(d2h_user(ctx, dst_xyz, a.key, sizeof(int32_t) * 3 * N, st));
-    } else {
-      HIP_TRY(qz_emit_launch(st, a, w, span));
-      HIP_TRY(d2h_user(ctx, dst_xyz, w.dst, sizeof(int32_t) * 3 * kept, st));
-      HIP_TRY(d2h_user(ctx, idx_to_src, w.idx_to_src, sizeof(int32_t) * kept, st));
-      HIP_TRY(d2h_user(ctx, src_dup_next, w.next, sizeof(int32_t) * N, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    *num_dst = (int32_t)kept;
-    return GPCC_OK;
-  };
-  r = run();
-  pool_free(ctx, d_src);
-  return r;
+  HIP_TRY(pool.take(3 * N, &d_src));
+  HIP_TRY(h2d_user(ctx, d_src, src_xyz, sizeof(int32_t) * 3 * N, st));
+  a.src = d_src;
+  auto span = [&](const char* name) { return Timer(ctx, name); };
+  HIP_TRY(qz_count_launch(st, a, w, max1, max2, span));
+  // the one host wait: the number of destination points and the error word
+  HIP_TRY(small_reset(ctx));
+  int32_t* h_count = (int32_t*)small_slot(ctx, sizeof(int32_t));
+  if (!h_count)
+    return fail(GPCC_ERR_HIP, "no pinned slot");
+  *h_count = n;
+  if (p->mode != 0)
+    HIP_TRY(hipMemcpyAsync(h_count, w.counts + w.num_tiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (ctx->h_error)
+    HIP_TRY(hipMemcpyAsync(ctx->h_error, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  r = check_device_error(ctx);
+  if (r)
+    return r;
+  const size_t kept = (size_t)*h_count;
+  if (p->mode == 0) {
+    HIP_TRY(d2h_user(ctx, dst_xyz, a.key, sizeof(int32_t) * 3 * N, st));
+  } else {
+    HIP_TRY(qz_emit_launch(st, a, w, span));
+    HIP_TRY(d2h_user(ctx, dst_xyz, w.dst, sizeof(int32_t) * 3 * kept, st));
+    HIP_TRY(d2h_user(ctx, idx_to_src, w.idx_to_src, sizeof(int32_t) * kept, st));
+    HIP_TRY(d2h_user(ctx, src_dup_next, w.next, sizeof(int32_t) * N, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  *num_dst = (int32_t)kept;
+  return GPCC_OK;
 }
 
 int
@@ -5876,17 +5849,18 @@ host_src_partition(
   a.listed = listed;
   a.num_slices = num_slices;
 
-  int32_t *d_sx = nullptr, *d_sa = nullptr, *d_map = nullptr, *d_next = nullptr, *d_idx = nullptr, *d_ioff = nullptr;
-  int32_t *d_ox = nullptr, *d_oa = nullptr;
+  PoolScope pool(ctx);
   int32_t* big = nullptr;
   auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_sx, sizeof(int32_t) * 3 * NS));
+    int32_t *d_sx = nullptr, *d_sa = nullptr, *d_map = nullptr, *d_next = nullptr, *d_idx = nullptr, *d_ioff = nullptr;
+    int32_t *d_ox = nullptr, *d_oa = nullptr;
+    HIP_TRY(pool.take(3 * NS, &d_sx));
     if (attrs)
-      HIP_TRY(pool_malloc(ctx, (void**)&d_sa, sizeof(int32_t) * c * NS));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_map, sizeof(int32_t) * ND));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_next, sizeof(int32_t) * NS));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_idx, sizeof(int32_t) * L));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_ioff, sizeof(int32_t) * S1));
+      HIP_TRY(pool.take(c * NS, &d_sa));
+    HIP_TRY(pool.take(ND, &d_map));
+    HIP_TRY(pool.take(NS, &d_next));
+    HIP_TRY(pool.take(L, &d_idx));
+    HIP_TRY(pool.take(S1, &d_ioff));
     // (the map and the lists first: the count pass needs nothing else)
     HIP_TRY(h2d_user(ctx, d_map, idx_to_src, sizeof(int32_t) * ND, st));
     HIP_TRY(h2d_user(ctx, d_next, src_dup_next, sizeof(int32_t) * NS, st));
@@ -5932,9 +5906,9 @@ host_src_partition(
     if (total == 0)
       return GPCC_OK;
     const size_t T = (size_t)total;
-    HIP_TRY(pool_malloc(ctx, (void**)&d_ox, sizeof(int32_t) * 3 * T));
+    HIP_TRY(pool.take(3 * T, &d_ox));
     if (attrs)
-      HIP_TRY(pool_malloc(ctx, (void**)&d_oa, sizeof(int32_t) * c * T));
+      HIP_TRY(pool.take(c * T, &d_oa));
     a.src_xyz = d_sx;
     a.src_attrs = d_sa;
     a.out_xyz = d_ox;
@@ -5948,17 +5922,9 @@ host_src_partition(
   };
   r = run();
   if (r)
-    hipStreamSynchronize(st);  // (uploads still in flight read the pooled blocks released below)
+    hipStreamSynchronize(st);  // (uploads still in flight read the pooled blocks released on return)
   if (big)
     hipHostFree(big);
-  pool_free(ctx, d_oa);
-  pool_free(ctx, d_ox);
-  pool_free(ctx, d_ioff);
-  pool_free(ctx, d_idx);
-  pool_free(ctx, d_next);
-  pool_free(ctx, d_map);
-  pool_free(ctx, d_sa);
-  pool_free(ctx, d_sx);
   return r;
 }
 
@@ -6788,14 +6754,13 @@ multi_transform(
   pin(morton, sizeof(int64_t) * (size_t)n_total);
   pin(attrs, sizeof(int32_t) * (size_t)n_total * c);
   pin(coeffs, sizeof(int32_t) * (size_t)n_total * c);
+  std::deque<PoolScope> pools;  // one per device: the parts' blocks, back in their pools when the call returns
+  for (int d = 0; d < nd; d++)
+    pools.emplace_back(m->ctx[d]);
   auto release = [&]() {
     for (void* q : pinned)
       hipHostUnregister(q);
-    for (int d = 0; d < nd; d++) {
-      auto& p = m->part[d];
-      pool_free(m->ctx[d], p.d_m);
-      pool_free(m->ctx[d], p.d_a);
-      pool_free(m->ctx[d], p.d_c);
+    for (auto& p : m->part) {
       p.d_m = nullptr;
       p.d_a = p.d_c = nullptr;
     }
@@ -6813,11 +6778,11 @@ multi_transform(
       const int64_t nbuf = (d == 0 && encoder) ? n_total : np;
       if (nbuf == 0)
         continue;
-      HIP_TRY(pool_malloc(ctx, (void**)&p.d_a, sizeof(int32_t) * std::max<int64_t>(np, 1) * c));
-      HIP_TRY(pool_malloc(ctx, (void**)&p.d_c, sizeof(int32_t) * nbuf * c));
+      HIP_TRY(pools[d].take((size_t)std::max<int64_t>(np, 1) * c, &p.d_a));
+      HIP_TRY(pools[d].take((size_t)nbuf * c, &p.d_c));
       if (np == 0)
         continue;
-      HIP_TRY(pool_malloc(ctx, (void**)&p.d_m, sizeof(int64_t) * np));
+      HIP_TRY(pools[d].take((size_t)np, &p.d_m));
       hipStream_t st = ctx->stream;
       // (device 0's part is the head of the batch: its buffers start at offset 0)
       HIP_TRY(hipMemcpyAsync(p.d_m, morton + b, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
@@ -7164,54 +7129,42 @@ binarise_symbols(
   hipStream_t st = ctx->stream;
   const size_t m = (size_t)num_symbols;
   const int nblk = (num_symbols + 1 + kBinBlock - 1) / kBinBlock;
+  PoolScope pool(ctx);
   int32_t *d_runs = nullptr, *d_vals = nullptr, *d_cnt = nullptr, *d_blk = nullptr;
   uint8_t* d_bins = nullptr;
   long long* d_base = nullptr;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_runs);
-    pool_free(ctx, d_vals);
-    pool_free(ctx, d_cnt);
-    pool_free(ctx, d_blk);
-    pool_free(ctx, d_base);
-    pool_free(ctx, d_bins);
-  };
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_runs, sizeof(int32_t) * (m + 1)));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_vals, sizeof(int32_t) * (m + 1) * c));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_cnt, sizeof(int32_t) * (m + 1)));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_blk, sizeof(int32_t) * ((size_t)nblk + 1)));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_base, sizeof(long long) * ((size_t)nblk + 1)));
-    if (m) {
-      HIP_TRY(h2d_user(ctx, d_runs, runs, sizeof(int32_t) * m, st));
-      HIP_TRY(h2d_user(ctx, d_vals, values, sizeof(int32_t) * m * c, st));
-    }
-    {
-      Timer t(ctx, "bins_count");
-      bins_count_kernel<<<nblk, kBinBlock, 0, st>>>(num_symbols, d_runs, d_vals, trailing_run, c, d_cnt, d_blk);
-      bins_scan_kernel<<<1, 1024, 0, st>>>(nblk, d_blk, d_base);
-    }
-    long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_base + nblk, sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *num_bins = total;
-    if (total > cap)
-      return fail(GPCC_ERR_INVALID_ARG, "bins buffer too small (see *num_bins)");
-    if (total == 0)
-      return GPCC_OK;
-    if (!bins)
-      return fail(GPCC_ERR_INVALID_ARG, "bins is null");
-    HIP_TRY(pool_malloc(ctx, (void**)&d_bins, (size_t)total));
-    {
-      Timer t(ctx, "bins_emit");
-      bins_emit_kernel<<<nblk, kBinBlock, 0, st>>>(num_symbols, d_runs, d_vals, trailing_run, c, d_cnt, d_base, d_bins);
-    }
-    HIP_TRY(d2h_user(ctx, bins, d_bins, (size_t)total, st));
-    HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(pool.take(m + 1, &d_runs));
+  HIP_TRY(pool.take((m + 1) * c, &d_vals));
+  HIP_TRY(pool.take(m + 1, &d_cnt));
+  HIP_TRY(pool.take((size_t)nblk + 1, &d_blk));
+  HIP_TRY(pool.take((size_t)nblk + 1, &d_base));
+  if (m) {
+    HIP_TRY(h2d_user(ctx, d_runs, runs, sizeof(int32_t) * m, st));
+    HIP_TRY(h2d_user(ctx, d_vals, values, sizeof(int32_t) * m * c, st));
+  }
+  {
+    Timer t(ctx, "bins_count");
+    bins_count_kernel<<<nblk, kBinBlock, 0, st>>>(num_symbols, d_runs, d_vals, trailing_run, c, d_cnt, d_blk);
+    bins_scan_kernel<<<1, 1024, 0, st>>>(nblk, d_blk, d_base);
+  }
+  long long total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_base + nblk, sizeof(long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *num_bins = total;
+  if (total > cap)
+    return fail(GPCC_ERR_INVALID_ARG, "bins buffer too small (see *num_bins)");
+  if (total == 0)
     return GPCC_OK;
-  };
-  int r = run();
-  cleanup();
-  return r;
+  if (!bins)
+    return fail(GPCC_ERR_INVALID_ARG, "bins is null");
+  HIP_TRY(pool.take((size_t)total, &d_bins));
+  {
+    Timer t(ctx, "bins_emit");
+    bins_emit_kernel<<<nblk, kBinBlock, 0, st>>>(num_symbols, d_runs, d_vals, trailing_run, c, d_cnt, d_base, d_bins);
+  }
+  HIP_TRY(d2h_user(ctx, bins, d_bins, (size_t)total, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GPCC_OK;
 }
 
 }  // namespace
@@ -7229,52 +7182,32 @@ gpcc_binarise_symbols(
 // ---- attribute transfer onto a re-quantised geometry (recolour_kernels.hpp) -----------
 namespace {
 
-// the working set of one tree's build, from the context's pool (recolour_kdtree.hpp)
-struct KdAlloc {
-  KdBuild b{};
-  std::vector<void*> blocks;
-};
-
+// one tree's build from the context's pool (recolour_kdtree.hpp): index array and nodes in `tree`, the build's
+// working set in `work`, which ends when the tree stands
 int
-kd_alloc(gpcc_ctx* ctx, KdAlloc* ka, const int32_t* d_xyz, int n)
+kd_alloc(PoolScope& tree, PoolScope& work, KdBuild& b, const int32_t* d_xyz, int n)
 {
   const size_t N = (size_t)n, M = 2 * N + 2;
-  auto take = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = pool_malloc(ctx, p, bytes);
-    if (e == hipSuccess)
-      ka->blocks.push_back(*p);
-    return e;
-  };
-  KdBuild& b = ka->b;
   b.t.xyz = d_xyz;
   b.t.n = n;
-  HIP_TRY(take((void**)&b.t.vind, sizeof(int32_t) * N));
+  HIP_TRY(tree.take_bytes(sizeof(int32_t) * N, (void**)&b.t.vind));
   b.node_cap = (int32_t)kd_node_capacity(N);
-  HIP_TRY(take((void**)&b.t.nodes, sizeof(KdNode) * kd_node_capacity(N)));
-  HIP_TRY(take((void**)&b.pnode, sizeof(int32_t) * N));
-  HIP_TRY(take((void**)&b.rng, sizeof(int32_t) * 2 * M));
-  HIP_TRY(take((void**)&b.parent, sizeof(int32_t) * M));
-  HIP_TRY(take((void**)&b.box, sizeof(double) * 6 * M));
-  HIP_TRY(take((void**)&b.mm, sizeof(int32_t) * 6 * M));
-  HIP_TRY(take((void**)&b.cut, sizeof(double) * M));
-  HIP_TRY(take((void**)&b.lim, sizeof(int32_t) * 2 * M));
-  HIP_TRY(take((void**)&b.split, sizeof(int32_t) * M));
-  HIP_TRY(take((void**)&b.flag, sizeof(int32_t) * (N + 1)));
-  HIP_TRY(take((void**)&b.tmp_l, sizeof(int32_t) * N));
-  HIP_TRY(take((void**)&b.tmp_r, sizeof(int32_t) * N));
-  HIP_TRY(take((void**)&b.sums, sizeof(long long) * ((N + 1) / kKdScanBlock + 2)));
-  HIP_TRY(take((void**)&b.counters, sizeof(int32_t) * 4));
-  HIP_TRY(take((void**)&b.sub_list, sizeof(int32_t) * 2 * (N / 11 + 2)));
+  HIP_TRY(tree.take_bytes(sizeof(KdNode) * kd_node_capacity(N), (void**)&b.t.nodes));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * N, (void**)&b.pnode));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * 2 * M, (void**)&b.rng));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * M, (void**)&b.parent));
+  HIP_TRY(work.take_bytes(sizeof(double) * 6 * M, (void**)&b.box));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * 6 * M, (void**)&b.mm));
+  HIP_TRY(work.take_bytes(sizeof(double) * M, (void**)&b.cut));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * 2 * M, (void**)&b.lim));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * M, (void**)&b.split));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * (N + 1), (void**)&b.flag));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * N, (void**)&b.tmp_l));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * N, (void**)&b.tmp_r));
+  HIP_TRY(work.take_bytes(sizeof(long long) * ((N + 1) / kKdScanBlock + 2), (void**)&b.sums));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * 4, (void**)&b.counters));
+  HIP_TRY(work.take_bytes(sizeof(int32_t) * 2 * (N / 11 + 2), (void**)&b.sub_list));
   return GPCC_OK;
-}
-
-void
-kd_release(gpcc_ctx* ctx, KdAlloc* ka, bool keep_tree)
-{
-  for (void* q : ka->blocks)
-    if (!(keep_tree && (q == (void*)ka->b.t.vind || q == (void*)ka->b.t.nodes)))
-      pool_free(ctx, q);
-  ka->blocks.clear();
 }
 
 int
@@ -7299,160 +7232,149 @@ recolour_impl(
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
 
+  PoolScope pool(ctx);
   int32_t *d_sx = nullptr, *d_sa = nullptr, *d_tx = nullptr, *d_out = nullptr, *d_box = nullptr;
   int32_t *d_ref1 = nullptr, *d_bt = nullptr, *d_lstart = nullptr, *d_lcur = nullptr, *d_lsrc = nullptr;
-  int32_t* d_near = nullptr;  // finite forward geometry limit: nearest source point per target, then the first limited target
   double *d_bd = nullptr, *d_ldist = nullptr;
   long long* d_sums = nullptr;
-  KdAlloc ks, kt;
-  auto cleanup = [&]() {
-    pool_free(ctx, d_near);
-    for (void* q : {(void*)d_sx, (void*)d_sa, (void*)d_tx, (void*)d_out, (void*)d_box, (void*)d_ref1,
-                    (void*)d_bt, (void*)d_lstart, (void*)d_lcur, (void*)d_lsrc, (void*)d_bd, (void*)d_ldist,
-                    (void*)d_sums})
-      pool_free(ctx, q);
-    kd_release(ctx, &ks, false);
-    kd_release(ctx, &kt, false);
+  HIP_TRY(pool.take(3 * (size_t)ns, &d_sx));
+  HIP_TRY(pool.take((size_t)c * ns, &d_sa));
+  HIP_TRY(pool.take(3 * (size_t)nt, &d_tx));
+  HIP_TRY(pool.take((size_t)c * nt, &d_out));
+  HIP_TRY(pool.take(12, &d_box));
+  HIP_TRY(h2d_user(ctx, d_sx, src_xyz, sizeof(int32_t) * 3 * (size_t)ns, st));
+  HIP_TRY(h2d_user(ctx, d_sa, src_attrs, sizeof(int32_t) * (size_t)c * ns, st));
+  HIP_TRY(h2d_user(ctx, d_tx, tgt_xyz, sizeof(int32_t) * 3 * (size_t)nt, st));
+  int32_t h_box[12];
+  for (int k = 0; k < 3; k++) {
+    h_box[k] = h_box[6 + k] = 0x7fffffff;
+    h_box[3 + k] = h_box[9 + k] = -0x7fffffff;
+  }
+  HIP_TRY(hipMemcpyAsync(d_box, h_box, sizeof(h_box), hipMemcpyHostToDevice, st));
+  {
+    Timer t(ctx, "rc_bbox");
+    // (few workgroups: every wavefront ends with six atomics on the same words)
+    rc_bbox_kernel<<<std::min(grid_for(ns, 256), 128), 256, 0, st>>>(d_sx, ns, d_box);
+    rc_bbox_kernel<<<std::min(grid_for(nt, 256), 128), 256, 0, st>>>(d_tx, nt, d_box + 6);
+  }
+  HIP_TRY(hipMemcpyAsync(h_box, d_box, sizeof(h_box), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int k = 0; k < 12; k++)
+    if (h_box[k] <= -(1 << 30) || h_box[k] >= (1 << 30))
+      return fail(GPCC_ERR_INVALID_ARG, "coordinates outside (-2^30, 2^30)");
+
+  RcCtx cx{};
+  int src_depth = 0, tgt_depth = 0;  // levels of the two k-d trees (GPCC_RC_DEBUG prints them)
+  cx.p = *p;
+  cx.c = c;
+  cx.s2t = (double)scale;
+  cx.t2s = 1.0 / (double)scale;
+  for (int k = 0; k < 3; k++)
+    cx.off[k] = offset[k];
+  cx.src_attrs = d_sa;
+
+  // ---- the two k-d trees, built together: the source's on the context's stream, the target's on
+  //      a second one (a level is a handful of small launches and a look at the node counter) ------
+  {
+    Timer t(ctx, "rc_kdtree");
+    // (the stream and the event are shared with inter-frame RAHT's second candidate)
+    if (!ctx->kd_stream)
+      HIP_TRY(hipStreamCreateWithFlags(&ctx->kd_stream, hipStreamNonBlocking));
+    if (!ctx->kd_event)
+      HIP_TRY(hipEventCreateWithFlags(&ctx->kd_event, hipEventDisableTiming));
+    if (!ctx->h_kd)
+      HIP_TRY(hipHostMalloc((void**)&ctx->h_kd, 8 * sizeof(int32_t)));
+    PoolScope work(ctx);  // (the builds' working sets go back to the pool here; index arrays and nodes stay)
+    KdBuild ks{}, kt{};
+    int r = kd_alloc(pool, work, ks, d_sx, ns);
+    if (!r)
+      r = kd_alloc(pool, work, kt, d_tx, nt);
+    if (r)
+      return r;
+    // (the second stream starts behind the uploads and the bounding boxes)
+    HIP_TRY(hipEventRecord(ctx->kd_event, st));
+    HIP_TRY(hipStreamWaitEvent(ctx->kd_stream, ctx->kd_event, 0));
+    KdLevelLoop loop[2];
+    HIP_TRY(loop[0].begin(ks, d_box, st, ctx->h_kd));
+    HIP_TRY(loop[1].begin(kt, d_box + 6, ctx->kd_stream, ctx->h_kd + 4));
+    while (!loop[0].done() || !loop[1].done()) {
+      for (int w = 0; w < 2; w++)
+        if (!loop[w].done())
+          HIP_TRY(loop[w].launch());
+      for (int w = 0; w < 2; w++)
+        if (!loop[w].done())
+          HIP_TRY(loop[w].finish());
+    }
+    // (the context's stream goes on behind the second one)
+    HIP_TRY(hipEventRecord(ctx->kd_event, ctx->kd_stream));
+    HIP_TRY(hipStreamWaitEvent(st, ctx->kd_event, 0));
+    for (int which = 0; which < 2; which++) {
+      if (loop[which].tree_depth() > kKdMaxDepth)
+        return fail(GPCC_ERR_UNSUPPORTED, "k-d tree deeper than 64 levels: it stays on the reference CPU path");
+      (which ? tgt_depth : src_depth) = loop[which].tree_depth();
+      KdTree& tr = which ? cx.tgt : cx.src;
+      tr = (which ? kt : ks).t;
+      for (int k = 0; k < 3; k++) {
+        tr.root_lo[k] = (double)h_box[6 * which + k];
+        tr.root_hi[k] = (double)h_box[6 * which + 3 + k];
+      }
+    }
+  }
+  static const bool rc_debug = [] {
+    const char* e = getenv("GPCC_RC_DEBUG");
+    return e && e[0] == '1';
+  }();
+  // (GPCC_RC_DEBUG=1: the trees' depths and a synchronisation + error check behind every stage)
+  auto stage_check = [&](const char* what) -> int {
+    if (!rc_debug)
+      return GPCC_OK;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess)
+      e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+      e = hipGetLastError();
+    fprintf(stderr, "gpcc recolour: %s: %s (ns %d nt %d depths %d %d)\n", what, hipGetErrorString(e), ns, nt, src_depth, tgt_depth);
+    return e == hipSuccess ? GPCC_OK : fail(GPCC_ERR_HIP, std::string("recolour stage ") + what + ": " + hipGetErrorString(e));
   };
-  auto run = [&]() -> int {
-    HIP_TRY(pool_malloc(ctx, (void**)&d_sx, sizeof(int32_t) * 3 * (size_t)ns));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_sa, sizeof(int32_t) * (size_t)c * ns));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_tx, sizeof(int32_t) * 3 * (size_t)nt));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_out, sizeof(int32_t) * (size_t)c * nt));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_box, sizeof(int32_t) * 12));
-    HIP_TRY(h2d_user(ctx, d_sx, src_xyz, sizeof(int32_t) * 3 * (size_t)ns, st));
-    HIP_TRY(h2d_user(ctx, d_sa, src_attrs, sizeof(int32_t) * (size_t)c * ns, st));
-    HIP_TRY(h2d_user(ctx, d_tx, tgt_xyz, sizeof(int32_t) * 3 * (size_t)nt, st));
-    int32_t h_box[12];
-    for (int k = 0; k < 3; k++) {
-      h_box[k] = h_box[6 + k] = 0x7fffffff;
-      h_box[3 + k] = h_box[9 + k] = -0x7fffffff;
-    }
-    HIP_TRY(hipMemcpyAsync(d_box, h_box, sizeof(h_box), hipMemcpyHostToDevice, st));
-    {
-      Timer t(ctx, "rc_bbox");
-      // (few workgroups: every wavefront ends with six atomics on the same words)
-      rc_bbox_kernel<<<std::min(grid_for(ns, 256), 128), 256, 0, st>>>(d_sx, ns, d_box);
-      rc_bbox_kernel<<<std::min(grid_for(nt, 256), 128), 256, 0, st>>>(d_tx, nt, d_box + 6);
-    }
-    HIP_TRY(hipMemcpyAsync(h_box, d_box, sizeof(h_box), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < 12; k++)
-      if (h_box[k] <= -(1 << 30) || h_box[k] >= (1 << 30))
-        return fail(GPCC_ERR_INVALID_ARG, "coordinates outside (-2^30, 2^30)");
+  {
+    int rd = stage_check("trees");
+    if (rd)
+      return rd;
+  }
+  const size_t total_cap = (size_t)ns * kb;
+  HIP_TRY(pool.take((size_t)c * nt, &d_ref1));
+  HIP_TRY(pool.take(total_cap, &d_bt));
+  HIP_TRY(pool.take(total_cap, &d_bd));
+  HIP_TRY(pool.take((size_t)nt + 1, &d_lstart));
+  HIP_TRY(pool.take((size_t)nt, &d_lcur));
+  HIP_TRY(pool.take(total_cap, &d_ldist));
+  HIP_TRY(pool.take(total_cap, &d_lsrc));
+  HIP_TRY(pool.take(((size_t)nt + 1) / kKdScanBlock + 2, &d_sums));
+  cx.ref1 = d_ref1;
+  if (p->max_geometry_dist2_fwd < 512) {
+    // finite forward geometry limit: nearest source point per target, then the first limited target
+    // (round 5: the reference's result vectors shrink for good at the first target beyond the limit)
+    int32_t* d_near = nullptr;
+    HIP_TRY(pool.take((size_t)nt + 1, &d_near));
+    cx.nearest = d_near;
+    cx.fwd_first = d_near + nt;
+    HIP_TRY(hipMemsetAsync(cx.fwd_first, 0x7f, sizeof(int32_t), st));
+  }
+  cx.bt = d_bt;
+  cx.bd = d_bd;
+  cx.lstart = d_lstart;
+  cx.lcur = d_lcur;
+  cx.ldist = d_ldist;
+  cx.lsrc = d_lsrc;
+  cx.out = d_out;
 
-    RcCtx cx{};
-    int src_depth = 0, tgt_depth = 0;  // levels of the two k-d trees (GPCC_RC_DEBUG prints them)
-    cx.p = *p;
-    cx.c = c;
-    cx.s2t = (double)scale;
-    cx.t2s = 1.0 / (double)scale;
-    for (int k = 0; k < 3; k++)
-      cx.off[k] = offset[k];
-    cx.src_attrs = d_sa;
-
-    // ---- the two k-d trees, built together: the source's on the context's stream, the target's on
-    //      a second one (a level is a handful of small launches and a look at the node counter) ------
-    {
-      Timer t(ctx, "rc_kdtree");
-      // (the stream and the event are shared with inter-frame RAHT's second candidate)
-      if (!ctx->kd_stream)
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->kd_stream, hipStreamNonBlocking));
-      if (!ctx->kd_event)
-        HIP_TRY(hipEventCreateWithFlags(&ctx->kd_event, hipEventDisableTiming));
-      if (!ctx->h_kd)
-        HIP_TRY(hipHostMalloc((void**)&ctx->h_kd, 8 * sizeof(int32_t)));
-      int r = kd_alloc(ctx, &ks, d_sx, ns);
-      if (!r)
-        r = kd_alloc(ctx, &kt, d_tx, nt);
-      if (r)
-        return r;
-      // (the second stream starts behind the uploads and the bounding boxes)
-      HIP_TRY(hipEventRecord(ctx->kd_event, st));
-      HIP_TRY(hipStreamWaitEvent(ctx->kd_stream, ctx->kd_event, 0));
-      KdLevelLoop loop[2];
-      HIP_TRY(loop[0].begin(ks.b, d_box, st, ctx->h_kd));
-      HIP_TRY(loop[1].begin(kt.b, d_box + 6, ctx->kd_stream, ctx->h_kd + 4));
-      while (!loop[0].done() || !loop[1].done()) {
-        for (int w = 0; w < 2; w++)
-          if (!loop[w].done())
-            HIP_TRY(loop[w].launch());
-        for (int w = 0; w < 2; w++)
-          if (!loop[w].done())
-            HIP_TRY(loop[w].finish());
-      }
-      // (the context's stream goes on behind the second one)
-      HIP_TRY(hipEventRecord(ctx->kd_event, ctx->kd_stream));
-      HIP_TRY(hipStreamWaitEvent(st, ctx->kd_event, 0));
-      for (int which = 0; which < 2; which++) {
-        if (loop[which].tree_depth() > kKdMaxDepth)
-          return fail(GPCC_ERR_UNSUPPORTED, "k-d tree deeper than 64 levels: it stays on the reference CPU path");
-        (which ? tgt_depth : src_depth) = loop[which].tree_depth();
-        KdAlloc& ka = which ? kt : ks;
-        KdTree& tr = which ? cx.tgt : cx.src;
-        tr = ka.b.t;
-        for (int k = 0; k < 3; k++) {
-          tr.root_lo[k] = (double)h_box[6 * which + k];
-          tr.root_hi[k] = (double)h_box[6 * which + 3 + k];
-        }
-        kd_release(ctx, &ka, true);  // (the build's working set goes back to the pool; index array and nodes stay)
-        ka.blocks.push_back((void*)tr.vind);
-        ka.blocks.push_back((void*)tr.nodes);
-      }
-    }
-    static const bool rc_debug = [] {
-      const char* e = getenv("GPCC_RC_DEBUG");
-      return e && e[0] == '1';
-    }();
-    // (GPCC_RC_DEBUG=1: the trees' depths and a synchronisation + error check behind every stage)
-    auto stage_check = [&](const char* what) -> int {
-      if (!rc_debug)
-        return GPCC_OK;
-      hipError_t e = hipStreamSynchronize(st);
-      if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-      if (e == hipSuccess)
-        e = hipGetLastError();
-      fprintf(stderr, "gpcc recolour: %s: %s (ns %d nt %d depths %d %d)\n", what, hipGetErrorString(e), ns, nt, src_depth, tgt_depth);
-      return e == hipSuccess ? GPCC_OK : fail(GPCC_ERR_HIP, std::string("recolour stage ") + what + ": " + hipGetErrorString(e));
-    };
-    {
-      int rd = stage_check("trees");
-      if (rd)
-        return rd;
-    }
-    const size_t total_cap = (size_t)ns * kb;
-    HIP_TRY(pool_malloc(ctx, (void**)&d_ref1, sizeof(int32_t) * (size_t)c * nt));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_bt, sizeof(int32_t) * total_cap));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_bd, sizeof(double) * total_cap));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_lstart, sizeof(int32_t) * ((size_t)nt + 1)));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_lcur, sizeof(int32_t) * (size_t)nt));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_ldist, sizeof(double) * total_cap));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_lsrc, sizeof(int32_t) * total_cap));
-    HIP_TRY(pool_malloc(ctx, (void**)&d_sums, sizeof(long long) * (((size_t)nt + 1) / kKdScanBlock + 2)));
-    cx.ref1 = d_ref1;
-    if (p->max_geometry_dist2_fwd < 512) {
-      // (round 5: the reference's result vectors shrink for good at the first target beyond the limit)
-      HIP_TRY(pool_malloc(ctx, (void**)&d_near, sizeof(int32_t) * ((size_t)nt + 1)));
-      cx.nearest = d_near;
-      cx.fwd_first = d_near + nt;
-      HIP_TRY(hipMemsetAsync(cx.fwd_first, 0x7f, sizeof(int32_t), st));
-    }
-    cx.bt = d_bt;
-    cx.bd = d_bd;
-    cx.lstart = d_lstart;
-    cx.lcur = d_lcur;
-    cx.ldist = d_ldist;
-    cx.lsrc = d_lsrc;
-    cx.out = d_out;
-
-    // ---- forward, backward, lists, blend ------------------------------------------------
-    {
-      Timer t(ctx, "rc_forward");
-      // list capacity 1 / 2 / 4 / 8 and with / without the attribute limit: 16 variants
-      const bool alimit = p->max_attribute_dist2_fwd < 512;
-      const int kcap = kf <= 1 ? 1 : kf <= 2 ? 2 : kf <= 4 ? 4 : 8;
-      const int fgrid = (nt + 255) / 256;
+  // ---- forward, backward, lists, blend ------------------------------------------------
+  {
+    Timer t(ctx, "rc_forward");
+    // list capacity 1 / 2 / 4 / 8 and with / without the attribute limit: 16 variants
+    const bool alimit = p->max_attribute_dist2_fwd < 512;
+    const int kcap = kf <= 1 ? 1 : kf <= 2 ? 2 : kf <= 4 ? 4 : 8;
+    const int fgrid = (nt + 255) / 256;
 #define GPCC_RC_FWD(CC, KK)                                                \
   do {                                                                     \
     if (alimit)                                                            \
@@ -7469,59 +7391,55 @@ recolour_impl(
     default: GPCC_RC_FWD(CC, 8); break;                                    \
     }                                                                      \
   } while (0)
-      if (c == 3)
-        GPCC_RC_FWD_K(3);
-      else
-        GPCC_RC_FWD_K(1);
+    if (c == 3)
+      GPCC_RC_FWD_K(3);
+    else
+      GPCC_RC_FWD_K(1);
 #undef GPCC_RC_FWD_K
 #undef GPCC_RC_FWD
-      if (cx.nearest)
-        rc_forward_limit_kernel<<<fgrid, 256, 0, st>>>(cx);
+    if (cx.nearest)
+      rc_forward_limit_kernel<<<fgrid, 256, 0, st>>>(cx);
+  }
+  {
+    int rd = stage_check("forward");
+    if (rd)
+      return rd;
+  }
+  HIP_TRY(hipMemsetAsync(d_lstart, 0, sizeof(int32_t) * ((size_t)nt + 1), st));
+  HIP_TRY(hipMemsetAsync(d_lcur, 0, sizeof(int32_t) * (size_t)nt, st));
+  {
+    Timer t(ctx, "rc_backward");
+    const int bgrid = (ns + 255) / 256;
+    switch (kb <= 1 ? 1 : kb <= 2 ? 2 : kb <= 4 ? 4 : 8) {
+    case 1: rc_backward_kernel<1><<<bgrid, 256, 0, st>>>(cx); break;
+    case 2: rc_backward_kernel<2><<<bgrid, 256, 0, st>>>(cx); break;
+    case 4: rc_backward_kernel<4><<<bgrid, 256, 0, st>>>(cx); break;
+    default: rc_backward_kernel<8><<<bgrid, 256, 0, st>>>(cx); break;
     }
-    {
-      int rd = stage_check("forward");
-      if (rd)
-        return rd;
-    }
-    HIP_TRY(hipMemsetAsync(d_lstart, 0, sizeof(int32_t) * ((size_t)nt + 1), st));
-    HIP_TRY(hipMemsetAsync(d_lcur, 0, sizeof(int32_t) * (size_t)nt, st));
-    {
-      Timer t(ctx, "rc_backward");
-      const int bgrid = (ns + 255) / 256;
-      switch (kb <= 1 ? 1 : kb <= 2 ? 2 : kb <= 4 ? 4 : 8) {
-      case 1: rc_backward_kernel<1><<<bgrid, 256, 0, st>>>(cx); break;
-      case 2: rc_backward_kernel<2><<<bgrid, 256, 0, st>>>(cx); break;
-      case 4: rc_backward_kernel<4><<<bgrid, 256, 0, st>>>(cx); break;
-      default: rc_backward_kernel<8><<<bgrid, 256, 0, st>>>(cx); break;
-      }
-    }
-    {
-      int rd = stage_check("backward");
-      if (rd)
-        return rd;
-    }
-    {
-      Timer t(ctx, "rc_lists");
-      int r = rc_scan(ctx, d_lstart, (size_t)nt + 1, d_sums);
-      if (r)
-        return r;
-      rc_list_fill_kernel<<<(ns + 255) / 256, 256, 0, st>>>(cx);
-    }
-    {
-      Timer t(ctx, "rc_blend");
-      if (c == 3)
-        rc_blend_kernel<3><<<(nt + 255) / 256, 256, 0, st>>>(cx);
-      else
-        rc_blend_kernel<1><<<(nt + 255) / 256, 256, 0, st>>>(cx);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(d2h_user(ctx, tgt_attrs, d_out, sizeof(int32_t) * (size_t)c * nt, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return GPCC_OK;
-  };
-  const int r = run();
-  cleanup();
-  return r;
+  }
+  {
+    int rd = stage_check("backward");
+    if (rd)
+      return rd;
+  }
+  {
+    Timer t(ctx, "rc_lists");
+    int r = rc_scan(ctx, d_lstart, (size_t)nt + 1, d_sums);
+    if (r)
+      return r;
+    rc_list_fill_kernel<<<(ns + 255) / 256, 256, 0, st>>>(cx);
+  }
+  {
+    Timer t(ctx, "rc_blend");
+    if (c == 3)
+      rc_blend_kernel<3><<<(nt + 255) / 256, 256, 0, st>>>(cx);
+    else
+      rc_blend_kernel<1><<<(nt + 255) / 256, 256, 0, st>>>(cx);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(d2h_user(ctx, tgt_attrs, d_out, sizeof(int32_t) * (size_t)c * nt, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GPCC_OK;
 }
 
 }  // namespace

@@ -1192,6 +1192,42 @@ int gpcc_recolour(
   int32_t c, float source_to_target_scale, const int32_t target_to_source_offset[3],
   int32_t* tgt_attrs);
 
+/* Every attribute of a slice in one call: what the encoder's loop over the attribute sets
+ * (tmc3/encoder.cpp:1031-1037, one pcc::recolour per set) computes, for up to GPCC_RC_MAX_ATTRS
+ * attributes on the same source and target positions.  attrs[a].tgt receives exactly what
+ * gpcc_recolour gives for attribute a alone with params->bitdepth = attrs[a].bitdepth, equidistant
+ * candidates included; an attribute's result does not depend on its neighbours in the call.
+ * SHARED (run once per call): the uploads of both position arrays, the bounding boxes, both k-d
+ * trees, the forward K-NN search of every target, `nearest` / the first limited target under a
+ * finite max_geometry_dist2_fwd, the backward search of every source point, the backward lists and
+ * their order.  That is exact because none of it reads an attribute: trees, neighbour indices and
+ * squared distances depend on positions, scale, offset and the parameters only, and std::sort's
+ * comparator (pointset_processing.cpp:416-422 / 770-777) looks at the distance alone, so the
+ * permutation it leaves a list in is the same whatever payload rides along.
+ * PER ATTRIBUTE: the gather of the neighbours' values, the max_attribute_dist2_* trimming (each
+ * attribute starts again from the full list), the averages, the round and the clip to the
+ * attribute's own bit depth, the +-search_range refinement; one upload and one download each.
+ * params->bitdepth is ignored.  Domain and declines as gpcc_recolour (counts <= 2^27, k 1..8,
+ * coordinates in (-2^30, 2^30); ns < num_neighbours_fwd, nt < num_neighbours_bwd or a tree deeper
+ * than 64 levels: GPCC_ERR_UNSUPPORTED).  GPCC_ERR_INVALID_ARG ahead of any launch: num_attrs
+ * outside 1 .. GPCC_RC_MAX_ATTRS, a c other than 1 or 3, a bit depth outside 1 .. 16, a null
+ * pointer, two attributes whose output buffers overlap.  On any failure no output buffer is
+ * written, the pooled blocks are back in the pool and the context works afterwards.  Host tier,
+ * synchronous: the results come down behind the last kernel, one wait at the end.  There is no
+ * device tier and gpcc_ctx_reserve does not cover the workspace. */
+#define GPCC_RC_MAX_ATTRS 4
+typedef struct gpcc_recolour_attr {
+  const int32_t* src;   /* [ns][c], values 0 .. 65535 */
+  int32_t* tgt;         /* [nt][c] out */
+  int32_t c;            /* 1 or 3 */
+  int32_t bitdepth;     /* 1 .. 16: this attribute's AttributeDescription::bitdepth */
+} gpcc_recolour_attr;
+
+int gpcc_recolour_attrs(
+  gpcc_ctx* ctx, const gpcc_recolour_params* params, const int32_t* src_xyz, int32_t ns,
+  const int32_t* tgt_xyz, int32_t nt, const gpcc_recolour_attr* attrs, int32_t num_attrs,
+  float source_to_target_scale, const int32_t target_to_source_offset[3]);
+
 /* ------------------------------------------------------------------ */
 /* unique-position quantisation and source partitions                   */
 

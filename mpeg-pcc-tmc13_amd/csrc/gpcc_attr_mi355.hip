@@ -7210,40 +7210,65 @@ kd_alloc(PoolScope& tree, PoolScope& work, KdBuild& b, const int32_t* d_xyz, int
   return GPCC_OK;
 }
 
+// Both entries run these stages.  `table` false: gpcc_recolour, one attribute through the kernels that take it
+// in RcCtx; true: gpcc_recolour_attrs, 1 .. GPCC_RC_MAX_ATTRS attributes through the kernels that take the table
+// -- everything in front of the forward tail and between it and the blend's tail runs once either way.
 int
 recolour_impl(
-  gpcc_ctx* ctx, const gpcc_recolour_params* p, const int32_t* src_xyz, const int32_t* src_attrs,
-  int32_t ns, const int32_t* tgt_xyz, int32_t nt, int32_t c, float scale, const int32_t* offset,
-  int32_t* tgt_attrs)
+  gpcc_ctx* ctx, const gpcc_recolour_params* p, const int32_t* src_xyz, int32_t ns, const int32_t* tgt_xyz,
+  int32_t nt, const gpcc_recolour_attr* attrs, int32_t num_attrs, bool table, float scale, const int32_t* offset)
 {
   if (!ctx)
     return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  if (!p || !src_xyz || !src_attrs || !tgt_xyz || !tgt_attrs || !offset || ns <= 0 || nt <= 0
-      || (c != 1 && c != 3))
+  if (table && (!attrs || num_attrs < 1 || num_attrs > GPCC_RC_MAX_ATTRS))
+    return fail(GPCC_ERR_INVALID_ARG, "attribute table is null or does not hold 1 .. GPCC_RC_MAX_ATTRS attributes");
+  bool attrs_ok = true;
+  for (int a = 0; a < num_attrs; a++)
+    attrs_ok = attrs_ok && attrs[a].src && attrs[a].tgt && (attrs[a].c == 1 || attrs[a].c == 3);
+  if (!p || !src_xyz || !tgt_xyz || !offset || ns <= 0 || nt <= 0 || !attrs_ok)
     return fail(GPCC_ERR_INVALID_ARG, "null buffer, empty cloud or attribute count not 1 / 3");
   if (ns > (1 << 27) || nt > (1 << 27))
     return fail(GPCC_ERR_INVALID_ARG, "more than 2^27 points");
   const int kf = p->num_neighbours_fwd, kb = p->num_neighbours_bwd;
-  if (kf < 1 || kf > kRcMaxK || kb < 1 || kb > kRcMaxK || p->bitdepth < 1 || p->bitdepth > 16
-      || p->search_range < 0 || !(scale > 0))
+  bool depth_ok = true;
+  for (int a = 0; a < num_attrs; a++)
+    depth_ok = depth_ok && attrs[a].bitdepth >= 1 && attrs[a].bitdepth <= 16;
+  if (kf < 1 || kf > kRcMaxK || kb < 1 || kb > kRcMaxK || !depth_ok || p->search_range < 0 || !(scale > 0))
     return fail(GPCC_ERR_INVALID_ARG, "neighbour counts must be 1..8, bitdepth 1..16, scale > 0");
+  for (int a = 0; a < num_attrs; a++)
+    for (int b = 0; b < a; b++) {
+      const uintptr_t a0 = (uintptr_t)attrs[a].tgt, a1 = a0 + sizeof(int32_t) * (size_t)attrs[a].c * nt;
+      const uintptr_t b0 = (uintptr_t)attrs[b].tgt, b1 = b0 + sizeof(int32_t) * (size_t)attrs[b].c * nt;
+      if (a0 < b1 && b0 < a1)
+        return fail(GPCC_ERR_INVALID_ARG, "two attributes name the same output buffer");
+    }
   if (ns < kf || nt < kb)
     return fail(GPCC_ERR_UNSUPPORTED, "fewer points than neighbours asked for");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
 
   PoolScope pool(ctx);
-  int32_t *d_sx = nullptr, *d_sa = nullptr, *d_tx = nullptr, *d_out = nullptr, *d_box = nullptr;
-  int32_t *d_ref1 = nullptr, *d_bt = nullptr, *d_lstart = nullptr, *d_lcur = nullptr, *d_lsrc = nullptr;
+  int32_t *d_sx = nullptr, *d_tx = nullptr, *d_box = nullptr;
+  int32_t *d_bt = nullptr, *d_lstart = nullptr, *d_lcur = nullptr, *d_lsrc = nullptr;
   double *d_bd = nullptr, *d_ldist = nullptr;
   long long* d_sums = nullptr;
+  RcAttrs at{};  // (the device's view of the attributes: source values, forward values, results)
+  at.n = num_attrs;
   HIP_TRY(pool.take(3 * (size_t)ns, &d_sx));
-  HIP_TRY(pool.take((size_t)c * ns, &d_sa));
+  int32_t* d_sa[GPCC_RC_MAX_ATTRS] = {};
+  for (int a = 0; a < num_attrs; a++) {
+    HIP_TRY(pool.take((size_t)attrs[a].c * ns, &d_sa[a]));
+    at.a[a].src = d_sa[a];
+    at.a[a].c = attrs[a].c;
+    at.a[a].clip_max = (1 << attrs[a].bitdepth) - 1;
+  }
   HIP_TRY(pool.take(3 * (size_t)nt, &d_tx));
-  HIP_TRY(pool.take((size_t)c * nt, &d_out));
+  for (int a = 0; a < num_attrs; a++)
+    HIP_TRY(pool.take((size_t)attrs[a].c * nt, &at.a[a].out));
   HIP_TRY(pool.take(12, &d_box));
   HIP_TRY(h2d_user(ctx, d_sx, src_xyz, sizeof(int32_t) * 3 * (size_t)ns, st));
-  HIP_TRY(h2d_user(ctx, d_sa, src_attrs, sizeof(int32_t) * (size_t)c * ns, st));
+  for (int a = 0; a < num_attrs; a++)
+    HIP_TRY(h2d_user(ctx, d_sa[a], attrs[a].src, sizeof(int32_t) * (size_t)attrs[a].c * ns, st));
   HIP_TRY(h2d_user(ctx, d_tx, tgt_xyz, sizeof(int32_t) * 3 * (size_t)nt, st));
   int32_t h_box[12];
   for (int k = 0; k < 3; k++) {
@@ -7266,12 +7291,15 @@ recolour_impl(
   RcCtx cx{};
   int src_depth = 0, tgt_depth = 0;  // levels of the two k-d trees (GPCC_RC_DEBUG prints them)
   cx.p = *p;
-  cx.c = c;
   cx.s2t = (double)scale;
   cx.t2s = 1.0 / (double)scale;
   for (int k = 0; k < 3; k++)
     cx.off[k] = offset[k];
-  cx.src_attrs = d_sa;
+  if (!table) {
+    cx.p.bitdepth = attrs[0].bitdepth;
+    cx.c = at.a[0].c;
+    cx.src_attrs = at.a[0].src;
+  }
 
   // ---- the two k-d trees, built together: the source's on the context's stream, the target's on
   //      a second one (a level is a handful of small launches and a look at the node counter) ------
@@ -7342,7 +7370,8 @@ recolour_impl(
       return rd;
   }
   const size_t total_cap = (size_t)ns * kb;
-  HIP_TRY(pool.take((size_t)c * nt, &d_ref1));
+  for (int a = 0; a < num_attrs; a++)
+    HIP_TRY(pool.take((size_t)attrs[a].c * nt, &at.a[a].ref1));
   HIP_TRY(pool.take(total_cap, &d_bt));
   HIP_TRY(pool.take(total_cap, &d_bd));
   HIP_TRY(pool.take((size_t)nt + 1, &d_lstart));
@@ -7350,7 +7379,10 @@ recolour_impl(
   HIP_TRY(pool.take(total_cap, &d_ldist));
   HIP_TRY(pool.take(total_cap, &d_lsrc));
   HIP_TRY(pool.take(((size_t)nt + 1) / kKdScanBlock + 2, &d_sums));
-  cx.ref1 = d_ref1;
+  if (!table) {
+    cx.ref1 = at.a[0].ref1;
+    cx.out = at.a[0].out;
+  }
   if (p->max_geometry_dist2_fwd < 512) {
     // finite forward geometry limit: nearest source point per target, then the first limited target
     // (round 5: the reference's result vectors shrink for good at the first target beyond the limit)
@@ -7366,7 +7398,6 @@ recolour_impl(
   cx.lcur = d_lcur;
   cx.ldist = d_ldist;
   cx.lsrc = d_lsrc;
-  cx.out = d_out;
 
   // ---- forward, backward, lists, blend ------------------------------------------------
   {
@@ -7391,14 +7422,34 @@ recolour_impl(
     default: GPCC_RC_FWD(CC, 8); break;                                    \
     }                                                                      \
   } while (0)
-    if (c == 3)
+#define GPCC_RC_FWD_ATTRS(KK)                                              \
+  do {                                                                     \
+    if (alimit)                                                            \
+      rc_forward_attrs_kernel<KK, true><<<fgrid, 256, 0, st>>>(cx, at);    \
+    else                                                                   \
+      rc_forward_attrs_kernel<KK, false><<<fgrid, 256, 0, st>>>(cx, at);   \
+  } while (0)
+    if (table) {
+      // (the kernel itself dispatches per attribute on c)
+      switch (kcap) {
+      case 1: GPCC_RC_FWD_ATTRS(1); break;
+      case 2: GPCC_RC_FWD_ATTRS(2); break;
+      case 4: GPCC_RC_FWD_ATTRS(4); break;
+      default: GPCC_RC_FWD_ATTRS(8); break;
+      }
+    } else if (cx.c == 3)
       GPCC_RC_FWD_K(3);
     else
       GPCC_RC_FWD_K(1);
+#undef GPCC_RC_FWD_ATTRS
 #undef GPCC_RC_FWD_K
 #undef GPCC_RC_FWD
-    if (cx.nearest)
-      rc_forward_limit_kernel<<<fgrid, 256, 0, st>>>(cx);
+    if (cx.nearest) {
+      if (table)
+        rc_forward_limit_attrs_kernel<<<fgrid, 256, 0, st>>>(cx, at);
+      else
+        rc_forward_limit_kernel<<<fgrid, 256, 0, st>>>(cx);
+    }
   }
   {
     int rd = stage_check("forward");
@@ -7431,13 +7482,16 @@ recolour_impl(
   }
   {
     Timer t(ctx, "rc_blend");
-    if (c == 3)
+    if (table)
+      rc_blend_attrs_kernel<<<(nt + 255) / 256, 256, 0, st>>>(cx, at);
+    else if (cx.c == 3)
       rc_blend_kernel<3><<<(nt + 255) / 256, 256, 0, st>>>(cx);
     else
       rc_blend_kernel<1><<<(nt + 255) / 256, 256, 0, st>>>(cx);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(d2h_user(ctx, tgt_attrs, d_out, sizeof(int32_t) * (size_t)c * nt, st));
+  for (int a = 0; a < num_attrs; a++)
+    HIP_TRY(d2h_user(ctx, attrs[a].tgt, at.a[a].out, sizeof(int32_t) * (size_t)attrs[a].c * nt, st));
   HIP_TRY(hipStreamSynchronize(st));
   return GPCC_OK;
 }
@@ -7450,10 +7504,21 @@ gpcc_recolour(
   const int32_t* src_attrs, int32_t ns, const int32_t* tgt_xyz, int32_t nt, int32_t c,
   float source_to_target_scale, const int32_t target_to_source_offset[3], int32_t* tgt_attrs)
 {
+  // (the one-attribute case of the driver, through the kernels it has always launched)
+  const gpcc_recolour_attr one = {src_attrs, tgt_attrs, c, params ? params->bitdepth : 0};
+  return counted(
+    ctx, recolour_impl(ctx, params, src_xyz, ns, tgt_xyz, nt, &one, 1, false, source_to_target_scale, target_to_source_offset),
+    nt);
+}
+
+extern "C" int
+gpcc_recolour_attrs(
+  gpcc_ctx* ctx, const gpcc_recolour_params* params, const int32_t* src_xyz, int32_t ns,
+  const int32_t* tgt_xyz, int32_t nt, const gpcc_recolour_attr* attrs, int32_t num_attrs,
+  float source_to_target_scale, const int32_t target_to_source_offset[3])
+{
   return counted(
     ctx,
-    recolour_impl(
-      ctx, params, src_xyz, src_attrs, ns, tgt_xyz, nt, c, source_to_target_scale,
-      target_to_source_offset, tgt_attrs),
+    recolour_impl(ctx, params, src_xyz, ns, tgt_xyz, nt, attrs, num_attrs, true, source_to_target_scale, target_to_source_offset),
     nt);
 }

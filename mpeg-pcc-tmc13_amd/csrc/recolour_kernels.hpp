@@ -225,6 +225,160 @@ rc_forward_kernel(RcCtx cx)
   }
 }
 
+// The attribute part of rc_forward_kernel, everything behind the search, for the kernel below: one attribute of C
+// components, `out` the target's row of its forward values.  rc_forward_kernel keeps its own text: calling
+// this function cost its <*, 8, false> forms a wavefront per SIMD and put <*, 4, false> into the 49..56 register
+// class (tools/isa_audit.py), so the two copies are to be kept in step.  (The contraction pragma is scoped to the
+// function it stands in: a fused multiply-add in a weight changes results at rounding ties.)
+template<int C, int K, bool ALIMIT>
+__device__ __forceinline__ void
+rc_forward_tail(const gpcc_recolour_params& p, const RcKnn<K>& r, const int32_t* src_attrs, int32_t* out, double max_a,
+                double clip_max)
+{
+#pragma clang fp contract(off)
+  // the neighbours' attributes, nearest first
+  int32_t col[K][C];
+#pragma unroll
+  for (int i = 0; i < K; i++)
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      col[i][k] = i < r.count ? src_attrs[(size_t)r.i[i] * C + k] : 0;
+  if (p.skip_avg_if_identical_fwd && r.d[0] < 0.0001) {
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      out[k] = col[0][k];
+    return;
+  }
+  // the largest attribute distance among the first m neighbours, for every m, computed ONCE (the
+  // reference recomputes all pairs for every candidate count, :341-349 / 692-699): pm[m] = max over
+  // i, j < m, both orders (colour differences wrap in 16 bits there: Vec3<attr_t> - Vec3<attr_t>,
+  // tmc3/PCCMath.h:280; reflectances are subtracted as int)
+  double pm[K + 1];
+#pragma unroll
+  for (int m = 0; m <= K; m++)
+    pm[m] = 2.2250738585072014e-308;
+  if (ALIMIT) {
+#pragma unroll
+    for (int m = 2; m <= K; m++) {
+      double best = pm[m - 1];
+#pragma unroll
+      for (int j = 0; j < m - 1; j++) {
+        double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < C; k++) {
+          const int32_t di = col[m - 1][k] - col[j][k];
+          const double d1 = C == 3 ? (double)(uint16_t)di : (double)di;
+          const double d2 = C == 3 ? (double)(uint16_t)(-di) : (double)(-di);
+          s1 += d1 * d1;
+          s2 += d2 * d2;
+        }
+        best = s1 > best ? s1 : best;
+        best = s2 > best ? s2 : best;
+      }
+      pm[m] = best;
+    }
+  }
+  for (int nn = r.count; nn > 0; nn--) {
+    if (nn == 1) {
+#pragma unroll
+      for (int k = 0; k < C; k++)
+        out[k] = col[0][k];
+      return;
+    }
+    double maxa = pm[1];
+#pragma unroll
+    for (int m = 2; m <= K; m++)
+      maxa = nn == m ? pm[m] : maxa;
+    if (maxa > max_a)
+      continue;
+    double acc[C];
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      acc[k] = 0.0;
+    if (p.use_dist_weighted_avg_fwd) {
+      double sumw = 0.0;
+#pragma unroll
+      for (int i = 0; i < K; i++) {
+        if (i < nn) {
+          const double w = 1 / (r.d[i] + p.dist_offset_fwd);
+#pragma unroll
+          for (int k = 0; k < C; k++)
+            acc[k] += (double)col[i][k] * w;
+          sumw += w;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < C; k++)
+        acc[k] /= sumw;
+    } else {
+#pragma unroll
+      for (int i = 0; i < K; i++) {
+        if (i < nn) {
+#pragma unroll
+          for (int k = 0; k < C; k++)
+            acc[k] += (double)col[i][k];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < C; k++)
+        acc[k] /= nn;
+    }
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      out[k] = (int32_t)rc_clip(round(acc[k]), 0.0, clip_max);
+    return;
+  }
+}
+
+// Up to GPCC_RC_MAX_ATTRS attributes of one source / target pair (gpcc_recolour_attrs): the searches, the
+// backward lists and their order read positions and parameters only, so they run once; what follows them runs
+// per attribute.  The table travels by value in the kernel argument.
+struct RcAttr {
+  const int32_t* src;  // [ns][c]
+  int32_t* ref1;       // [nt][c] forward values
+  int32_t* out;        // [nt][c]
+  int32_t c;           // 1 or 3
+  int32_t clip_max;    // (1 << bitdepth) - 1
+};
+
+struct RcAttrs {
+  RcAttr a[GPCC_RC_MAX_ATTRS];
+  int32_t n;
+};
+
+// forward for every attribute of the table: ONE search per target, then the tail per attribute (the loop and
+// its dispatch on c are uniform across the wavefront; ALIMIT as in rc_forward_kernel)
+template<int K, bool ALIMIT>
+__global__ __launch_bounds__(256) GPCC_RC_OCCUPANCY void
+rc_forward_attrs_kernel(RcCtx cx, RcAttrs at)
+{
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cx.tgt.n)
+    return;
+  const gpcc_recolour_params& p = cx.p;
+  const int kf = p.num_neighbours_fwd;
+  const double max_a = rc_limit(p.max_attribute_dist2_fwd);
+  double q[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    q[a] = (double)(cx.tgt.xyz[3 * t + a] + cx.off[a]) * cx.t2s;
+  RcKnn<K> r;
+  rc_kd_search<K>(cx.src, q, kf, r);
+  if (cx.nearest) {
+    cx.nearest[t] = r.i[0];
+    if (rc_worst(r, kf) > rc_limit(p.max_geometry_dist2_fwd))
+      atomicMin(cx.fwd_first, t);
+  }
+  for (int a = 0; a < at.n; a++) {
+    const RcAttr& A = at.a[a];
+    if (A.c == 3)
+      rc_forward_tail<3, K, ALIMIT>(p, r, A.src, A.ref1 + (size_t)t * 3, max_a, (double)A.clip_max);
+    else
+      rc_forward_tail<1, K, ALIMIT>(p, r, A.src, A.ref1 + t, max_a, (double)A.clip_max);
+  }
+}
+
 // the targets from the first one beyond a finite forward geometry limit on: the colour of the nearest source
 // point (the reference's result vectors hold one entry from there, pointset_processing.cpp:304-313, 329-334)
 __global__ __launch_bounds__(256) void
@@ -235,6 +389,21 @@ rc_forward_limit_kernel(RcCtx cx)
     return;
   for (int k = 0; k < cx.c; k++)
     cx.ref1[(size_t)t * cx.c + k] = cx.src_attrs[(size_t)cx.nearest[t] * cx.c + k];
+}
+
+// ... for every attribute of the table
+__global__ __launch_bounds__(256) void
+rc_forward_limit_attrs_kernel(RcCtx cx, RcAttrs at)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cx.tgt.n || t < *cx.fwd_first)
+    return;
+  const int32_t s = cx.nearest[t];
+  for (int a = 0; a < at.n; a++) {
+    const RcAttr& A = at.a[a];
+    for (int k = 0; k < A.c; k++)
+      A.ref1[(size_t)t * A.c + k] = A.src[(size_t)s * A.c + k];
+  }
 }
 
 // ---- backward (:386-424 / 730-766): nearest targets of every source point ------------
@@ -439,31 +608,11 @@ rc_std_sort(double* d, int32_t* s, int n)
 }
 
 // ---- blend and refinement (:426-592 / 768-914) ---------------------------------------
-template<int C>
-__global__ __launch_bounds__(256) void
-rc_blend_kernel(RcCtx cx)
+// the reference pushes a target's entries in source order (:397-412; the fill order here is
+// whatever the atomics made it), then std::sort orders them by distance alone (:416-422)
+__device__ __forceinline__ void
+rc_list_order(double* ld, int32_t* ls, int n)
 {
-#pragma clang fp contract(off)
-  GPCC_VGPR_FLOOR_64();
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= cx.tgt.n)
-    return;
-  const gpcc_recolour_params& p = cx.p;
-  const int32_t* __restrict__ sa = cx.src_attrs;
-  const int l0 = cx.lstart[t];
-  int n = cx.lstart[t + 1] - l0;
-  double* ld = cx.ldist + l0;
-  int32_t* ls = cx.lsrc + l0;
-  const int32_t* c1 = cx.ref1 + (size_t)t * C;
-  int32_t* out = cx.out + (size_t)t * C;
-  if (n == 0) {
-#pragma unroll
-    for (int k = 0; k < C; k++)
-      out[k] = c1[k];
-    return;
-  }
-  // the reference pushes a target's entries in source order (:397-412; the fill order here is
-  // whatever the atomics made it), then std::sort orders them by distance alone (:416-422)
   for (int i = 1; i < n; i++) {
     const double d = ld[i];
     const int32_t s = ls[i];
@@ -477,8 +626,18 @@ rc_blend_kernel(RcCtx cx)
     ls[j] = s;
   }
   rc_std_sort(ld, ls, n);
+}
+
+// The attribute part of one target's blend: its ordered list of n >= 1 entries (distances ld, source points ls),
+// one attribute of C components; c1 / out are the target's rows of the forward values and of the result.  n is
+// this attribute's own copy: the trimming under max_attribute_dist2_bwd depends on the values.
+template<int C>
+__device__ __forceinline__ void
+rc_blend_tail(const gpcc_recolour_params& p, const double* ld, const int32_t* ls, int n, const int32_t* __restrict__ sa,
+              const int32_t* c1, int32_t* out, double clip_max, double r_source, double r_target)
+{
+#pragma clang fp contract(off)
   const double max_a = rc_limit(p.max_attribute_dist2_bwd);
-  const double clip_max = (double)((1 << p.bitdepth) - 1);
   double cen2[C];
 #pragma unroll
   for (int k = 0; k < C; k++)
@@ -545,8 +704,6 @@ rc_blend_kernel(RcCtx cx)
     c0[k] = rc_clip(round(0.0 * (double)c1[k] + 1.0 * cen2[k]), 0.0, clip_max);
     best[k] = col[k] = c0[k];
   }
-  const double r_source = 1.0 / (double)cx.src.n;
-  const double r_target = 1.0 / (double)cx.tgt.n;
   double min_err = 1.7976931348623157e308;
   const int sr = p.search_range;
   const int n1 = C == 3 ? sr : 0;
@@ -586,6 +743,68 @@ rc_blend_kernel(RcCtx cx)
 #pragma unroll
   for (int k = 0; k < C; k++)
     out[k] = (int32_t)best[k];
+}
+
+template<int C>
+__global__ __launch_bounds__(256) void
+rc_blend_kernel(RcCtx cx)
+{
+#pragma clang fp contract(off)
+  GPCC_VGPR_FLOOR_64();
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cx.tgt.n)
+    return;
+  const int l0 = cx.lstart[t];
+  const int n = cx.lstart[t + 1] - l0;
+  double* ld = cx.ldist + l0;
+  int32_t* ls = cx.lsrc + l0;
+  const int32_t* c1 = cx.ref1 + (size_t)t * C;
+  int32_t* out = cx.out + (size_t)t * C;
+  if (n == 0) {
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      out[k] = c1[k];
+    return;
+  }
+  rc_list_order(ld, ls, n);
+  rc_blend_tail<C>(cx.p, ld, ls, n, cx.src_attrs, c1, out, (double)((1 << cx.p.bitdepth) - 1), 1.0 / (double)cx.src.n,
+                   1.0 / (double)cx.tgt.n);
+}
+
+// blend for every attribute of the table: the list is put in order ONCE (std::sort's comparator sees the
+// distances alone, so the permutation is the same whatever payload rides along), then the tail per attribute,
+// each from the full list length
+__global__ __launch_bounds__(256) void
+rc_blend_attrs_kernel(RcCtx cx, RcAttrs at)
+{
+#pragma clang fp contract(off)
+  GPCC_VGPR_FLOOR_64();
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cx.tgt.n)
+    return;
+  const int l0 = cx.lstart[t];
+  const int n = cx.lstart[t + 1] - l0;
+  double* ld = cx.ldist + l0;
+  int32_t* ls = cx.lsrc + l0;
+  if (n == 0) {
+    for (int a = 0; a < at.n; a++) {
+      const RcAttr& A = at.a[a];
+      for (int k = 0; k < A.c; k++)
+        A.out[(size_t)t * A.c + k] = A.ref1[(size_t)t * A.c + k];
+    }
+    return;
+  }
+  rc_list_order(ld, ls, n);
+  const double r_source = 1.0 / (double)cx.src.n;
+  const double r_target = 1.0 / (double)cx.tgt.n;
+  for (int a = 0; a < at.n; a++) {
+    const RcAttr& A = at.a[a];
+    if (A.c == 3)
+      rc_blend_tail<3>(cx.p, ld, ls, n, A.src, A.ref1 + (size_t)t * 3, A.out + (size_t)t * 3, (double)A.clip_max, r_source,
+                       r_target);
+    else
+      rc_blend_tail<1>(cx.p, ld, ls, n, A.src, A.ref1 + t, A.out + t, (double)A.clip_max, r_source, r_target);
+  }
 }
 
 }  // namespace gpcc

@@ -298,6 +298,14 @@ class RecolourParams(C.Structure):
     ]
 
 
+GPCC_RC_MAX_ATTRS = 4
+
+
+class RecolourAttr(C.Structure):
+    """ctypes mirror of gpcc_recolour_attr: one attribute of a gpcc_recolour_attrs call."""
+    _fields_ = [("src", C.c_void_p), ("tgt", C.c_void_p), ("c", C.c_int32), ("bitdepth", C.c_int32)]
+
+
 def recolour_params(bitdepth=8, search_range=1, k_fwd=8, k_bwd=1, weighted_fwd=True, weighted_bwd=True,
                     skip_fwd=True, skip_bwd=False, dist_offset_fwd=4.0, dist_offset_bwd=4.0,
                     max_geom_fwd=1000.0, max_geom_bwd=1000.0, max_attr_fwd=1000.0, max_attr_bwd=1000.0):

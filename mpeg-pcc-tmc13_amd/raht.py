@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .params import RahtParams
+from .params import RahtParams, RecolourAttr
 
 
 class Context:
@@ -474,6 +474,35 @@ class Context:
             self._h, C.byref(params), sx.ctypes.data, sa.ctypes.data, ns, tx.ctypes.data, nt, c,
             C.c_float(scale), off, out.ctypes.data))
         return out
+
+    def recolour_attrs(self, params, src_xyz, attrs, tgt_xyz, scale=1.0, offset=(0, 0, 0), fill=None):
+        """gpcc_recolour_attrs: every attribute of a slice in one call (the encoder's loop over its attribute sets,
+        encoder.cpp:1031-1037) -- the searches, the trees and the backward lists once, the blends per attribute.
+        attrs: a list of (array [ns, c], bitdepth); params.bitdepth is ignored -> a list of int32 [nt, c], each what
+        recolour() gives for that attribute alone.  fill: what the output buffers hold before the call (tests); on an
+        error they are attached to the raised GpccError as `buffers`."""
+        sx = np.ascontiguousarray(src_xyz, dtype=np.int32)
+        tx = np.ascontiguousarray(tgt_xyz, dtype=np.int32)
+        ns, nt = sx.shape[0], tx.shape[0]
+        srcs, outs = [], []
+        table = (RecolourAttr * max(len(attrs), 1))()
+        for i, (a, bitdepth) in enumerate(attrs):
+            sa = np.ascontiguousarray(a, dtype=np.int32).reshape(ns, -1)
+            out = np.full((nt, sa.shape[1]), 0 if fill is None else fill, dtype=np.int32)
+            srcs.append(sa)
+            outs.append(out)
+            table[i].src, table[i].tgt = sa.ctypes.data, out.ctypes.data
+            table[i].c, table[i].bitdepth = sa.shape[1], int(bitdepth)
+        off = (C.c_int32 * 3)(*[int(v) for v in offset])
+        rc = self._lib.gpcc_recolour_attrs(self._h, C.byref(params), sx.ctypes.data, ns, tx.ctypes.data, nt, table,
+                                           len(attrs), C.c_float(scale), off)
+        if rc != 0:
+            try:
+                _lib.check(rc)
+            except _lib.GpccError as e:
+                e.buffers = outs
+                raise
+        return outs
 
     # ---- unique-position quantisation and source partitions ---------------
     def quantize_positions(self, params, src_xyz, fill=None):

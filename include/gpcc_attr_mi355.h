@@ -409,6 +409,14 @@ typedef struct gpcc_lift_params {
  *   indexes     [n]     AttributeLods::indexes: predictor order -> point index
  *   qp_off      [n][2]  region QP offset of each POINT (QpSet::regionQpOffset),
  *                       NULL = none
+ * The lifting entries that take the caller's predictors (gpcc_lift_forward,
+ * _inverse, _inverse_partial, _forward_inter, _inverse_inter) run a level of
+ * detail as one parallel step: every neighbour of a predictor of level l lies
+ * in a COARSER level, neigh_index < num_points_in_lod[l - 1], and a predictor
+ * of level 0 has none (the reference's assert, PCCTMC3Common.h:805).  Anything
+ * else is GPCC_ERR_INVALID_ARG; neighbours in the reference frame (inter_ref)
+ * are exempt.  The predicting entries walk the predictors in order and accept
+ * any neigh_index below the predictor's own.
  * Forward: replaces the body of encodeColorsLift / encodeReflectancesLift
  * minus the entropy calls.  attrs [n][c] in point order: in source, out the
  * reconstructed (rounded, clipped) attributes, as the reference writes them

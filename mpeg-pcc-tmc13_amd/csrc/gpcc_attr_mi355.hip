@@ -2413,6 +2413,7 @@ struct LiftCoder {
   using Frame = CoderFrame;
   static constexpr int32_t kMaxN = kMaxPoints;
   static constexpr size_t kSideBytes = GPCC_MAX_LODS;
+  static constexpr bool kCoarserNeighboursOnly = true;  // a level of detail is one parallel step
   static constexpr const char* kBadCount = "null buffer or attribute count not 1..3";
   static constexpr const char* kSideNull = "lcp_coeffs is null";
   static constexpr const char* kInterOnly =
@@ -2447,6 +2448,7 @@ struct PredCoder {
   using Frame = CoderFrame;
   static constexpr int32_t kMaxN = 1 << 27;
   static constexpr size_t kSideBytes = GPCC_MAX_LODS * 3;
+  static constexpr bool kCoarserNeighboursOnly = false;  // sequential over the predictors
   static constexpr const char* kBadCount = "null buffer or attribute count not 1 / 3";
   static constexpr const char* kSideNull = "icp_coeffs is null";
   static constexpr const char* kInterOnly =
@@ -2474,14 +2476,22 @@ struct PredCoder {
 
 // ---- host tier: the caller brings the predictors ---------------------------------------------
 
-// inter_ref [n][3] (null: none) marks the neighbours that live in the reference frame: ni is then a point index there
+// inter_ref [n][3] (null: none) marks the neighbours that live in the reference frame: ni is then a point index there.
+// npl (null: the predicting transform, which walks the predictors one by one and allows neighbours inside the
+// level): the cumulative LoD sizes of the lifting transform, whose kernels take a level of detail as one parallel
+// step -- every neighbour of the slice itself lies in a COARSER level (the reference's assert, PCCTMC3Common.h:805)
 int
 check_neighbour_tables(
-  int n, const int32_t* nc, const int32_t* ni, const int32_t* indexes, const int32_t* inter_ref, int n_frame)
+  int n, const int32_t* nc, const int32_t* ni, const int32_t* indexes, const int32_t* inter_ref, int n_frame,
+  const int32_t* npl = nullptr, int num_lods = 0)
 {
+  int l = 0;
   for (int i = 0; i < n; i++) {
     if (nc[i] < 0 || nc[i] > 3 || indexes[i] < 0 || indexes[i] >= n)
       return fail(GPCC_ERR_INVALID_ARG, "bad neighbour count / index table");
+    while (npl && l < num_lods - 1 && i >= npl[l])
+      l++;
+    const int32_t coarser = l ? npl[l - 1] : 0;  // (lifting) where the predictor's level starts
     for (int j = 0; j < nc[i]; j++) {
       const int32_t v = ni[3 * (size_t)i + j];
       if (inter_ref && inter_ref[3 * (size_t)i + j]) {
@@ -2489,6 +2499,8 @@ check_neighbour_tables(
           return fail(GPCC_ERR_INVALID_ARG, "a neighbour outside the reference frame");
       } else if (v < 0 || v >= i)
         return fail(GPCC_ERR_INVALID_ARG, "a neighbour does not precede its predictor");
+      else if (npl && v >= coarser)
+        return fail(GPCC_ERR_INVALID_ARG, "lifting: a neighbour is not in a coarser level of detail than its predictor");
     }
   }
   return GPCC_OK;
@@ -2540,7 +2552,9 @@ host_lod_coder(
       return fail(GPCC_ERR_UNSUPPORTED, Coder::kInterOnly);
   } else
     n_frame = 0;
-  rcode = check_neighbour_tables(n, nc, ni, indexes, inter_ref, n_frame);
+  rcode = check_neighbour_tables(
+    n, nc, ni, indexes, inter_ref, n_frame, Coder::kCoarserNeighboursOnly ? p->num_points_in_lod : nullptr,
+    p->num_lods);
   if (rcode)
     return rcode;
   std::vector<int32_t> ni_frame;

@@ -79,6 +79,52 @@ def test_lift_rejects_bad_structure(ctx):
         ctx.lift_forward(lf, nc, ni, w, np.arange(3, dtype=np.int32), np.zeros((3, 1), np.int32))
 
 
+def test_lift_rejects_neighbour_inside_its_level(ctx):
+    """The lifting kernels take a level of detail as one parallel step, so every neighbour lies in a COARSER
+    level (the reference's assert, PCCTMC3Common.h:805); `ni < i` alone lets a neighbour of the predictor's own
+    level through, and the result then depends on timing.  Encoder and decoder refuse, touch no output, hold no
+    pool block, and the context serves the next valid call."""
+    import ctypes as C
+    from mpeg_pcc_tmc13_amd import lift_params
+    lib, sentinel = ctx._lib, -77
+    lf = lift_params([2, 4, 6], qp=20, lcp=False)
+    nc = np.array([0, 0, 1, 1, 1, 1], np.int32)
+    ni = np.array([[0, 0, 0], [0, 0, 0], [0, 0, 0], [1, 0, 0], [2, 0, 0], [4, 0, 0]], np.int32)  # 5 -> 4: its own level
+    w = np.full((6, 3), 256, np.int32)
+    ix = np.arange(6, dtype=np.int32)
+    lib.gpcc_debug_pool_in_use.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+
+    def pool():
+        out = (C.c_longlong * 2)()
+        assert lib.gpcc_debug_pool_in_use(ctx._h, out) == 0
+        return list(out)
+
+    for fn in (lib.gpcc_lift_forward, lib.gpcc_lift_inverse):
+        a = np.full((6, 1), sentinel, np.int32)
+        co = np.full((6, 1), sentinel, np.int32)
+        lcp = np.full(32, sentinel, np.int8)
+        rc = fn(ctx._h, C.byref(lf), 6, 1, nc.ctypes.data, ni.ctypes.data, w.ctypes.data, ix.ctypes.data, None,
+                a.ctypes.data, co.ctypes.data, lcp.ctypes.data)
+        assert rc == -1  # GPCC_ERR_INVALID_ARG
+        assert b"coarser level" in lib.gpcc_last_error()
+        assert (a == sentinel).all() and (co == sentinel).all() and (lcp == sentinel).all()
+        assert pool() == [0, 0]
+    # a neighbour at level 0 has no coarser level to lie in
+    nc0 = np.array([0, 1, 1, 1, 1, 1], np.int32)
+    ni0 = ni.copy()
+    ni0[5, 0] = 3
+    a = np.full((6, 1), sentinel, np.int32)
+    co = np.full((6, 1), sentinel, np.int32)
+    rc = lib.gpcc_lift_forward(ctx._h, C.byref(lf), 6, 1, nc0.ctypes.data, ni0.ctypes.data, w.ctypes.data,
+                               ix.ctypes.data, None, a.ctypes.data, co.ctypes.data, None)
+    assert rc == -1 and (a == sentinel).all() and (co == sentinel).all() and pool() == [0, 0]
+    # the same table with that neighbour one level down is served
+    ctx.lift_forward(lf, nc, ni0, w, ix, np.arange(6, dtype=np.int32).reshape(6, 1))
+    # and the context gives the fixture's result afterwards
+    test_lift_vs_golden("rand2k_layers", ctx)
+    assert pool() == [0, 0]
+
+
 @pytest.mark.parametrize("kind,n,kw", [("dense", 60000, {}), ("lidar", 40000, dict(decimation=1)),
                                        ("dense", 3000, dict(decimation=2)), ("random", 5, {}), ("random", 1, {})])
 def test_lift_attr_driver_matches_composition(kind, n, kw, ctx):

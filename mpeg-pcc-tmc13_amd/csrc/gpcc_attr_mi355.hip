@@ -3270,59 +3270,63 @@ gpcc_ctx_kernel_times(gpcc_ctx* ctx, gpcc_kernel_time* out, int32_t max_entries)
   return nout;
 }
 
-static int
-dev_morton_sort(
-  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz,
-  void* d_morton, void* d_order)
+// ---- Morton sort (morton_sort.hpp): scratch, launch sequence, entry -----------------------------------------
+
+// slice boundaries and the tiles of kSortTile keys; tiles never straddle a slice
+struct SortTiles {
+  std::vector<int32_t> off, first, count, slice;
+  int n() const { return off.back(); }
+  int num_slices() const { return (int)off.size() - 1; }
+  int nt() const { return (int)first.size(); }
+};
+
+static SortTiles
+sort_tiles(int32_t num_slices, const int64_t* offsets)
 {
-  if (!ctx)
-    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
-  if (num_slices < 1 || !offsets || offsets[0] != 0 || !d_xyz || !d_morton || !d_order)
-    return fail(GPCC_ERR_INVALID_ARG, "bad arguments");
-  for (int i = 0; i < num_slices; i++)
-    if (offsets[i + 1] <= offsets[i])
-      return fail(GPCC_ERR_INVALID_ARG, "empty or unordered slice");
-  if (offsets[num_slices] > kMaxPoints)
-    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per batch");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int n = (int)offsets[num_slices];
-  const int bits = ctx->morton_bits > 0 ? ctx->morton_bits : 63;
-  const int passes = std::max(1, (bits + 7) / 8);
-
-  // tiles never straddle a slice
-  std::vector<int32_t> h_off(num_slices + 1), t_first, t_count, t_slice;
+  SortTiles t;
+  t.off.resize(num_slices + 1);
   for (int s = 0; s <= num_slices; s++)
-    h_off[s] = (int32_t)offsets[s];
+    t.off[s] = (int32_t)offsets[s];
   for (int s = 0; s < num_slices; s++)
-    for (int b = h_off[s]; b < h_off[s + 1]; b += kSortTile) {
-      t_first.push_back(b);
-      t_count.push_back(std::min(kSortTile, h_off[s + 1] - b));
-      t_slice.push_back(s);
+    for (int b = t.off[s]; b < t.off[s + 1]; b += kSortTile) {
+      t.first.push_back(b);
+      t.count.push_back(std::min(kSortTile, t.off[s + 1] - b));
+      t.slice.push_back(s);
     }
-  const int nt = (int)t_first.size();
+  return t;
+}
 
-  Arena measure;
-  auto carve_sort = [&](Arena& ar, SortCtx& cx, int64_t*& kbuf, int32_t*& vbuf,
-                        int32_t*& pt_off) {
-    ar.reset();
-    pt_off = ar.take<int32_t>(num_slices + 1);
-    cx.tile_first = ar.take<int32_t>(nt);
-    cx.tile_count = ar.take<int32_t>(nt);
-    cx.tile_slice = ar.take<int32_t>(nt);
-    cx.hist = ar.take<uint32_t>((size_t)256 * nt);
-    kbuf = ar.take<int64_t>(n);
-    vbuf = ar.take<int32_t>(n);
-  };
-  SortCtx cx{};
+struct SortWork {
+  SortCtx cx{};  // the tile tables and the histograms
   int64_t* kbuf = nullptr;
   int32_t* vbuf = nullptr;
-  int32_t* d_pt = nullptr;
-  carve_sort(measure, cx, kbuf, vbuf, d_pt);
-  int rcode = ensure_arena(ctx, measure.used);
-  if (rcode)
-    return rcode;
-  carve_sort(ctx->arena, cx, kbuf, vbuf, d_pt);
+  int32_t* pt_off = nullptr;
+};
+
+// scratch of a sort of up to n keys in num_slices slices and nt tiles.  With ar.base == nullptr this only measures.
+static void
+carve_sort(Arena& ar, SortWork& w, int n, int num_slices, int nt)
+{
+  w.pt_off = ar.take<int32_t>(num_slices + 1);
+  w.cx.tile_first = ar.take<int32_t>(nt);
+  w.cx.tile_count = ar.take<int32_t>(nt);
+  w.cx.tile_slice = ar.take<int32_t>(nt);
+  w.cx.hist = ar.take<uint32_t>((size_t)256 * nt);
+  w.kbuf = ar.take<int64_t>(n);
+  w.vbuf = ar.take<int32_t>(n);
+}
+
+// keys of `bits` significant bits; `w` was carved for at least these tiles
+static int
+sort_run(
+  gpcc_ctx* ctx, const SortWork& w, int bits, const SortTiles& t, const void* d_xyz, void* d_morton, void* d_order)
+{
+  hipStream_t st = ctx->stream;
+  const int n = t.n(), nt = t.nt(), num_slices = t.num_slices();
+  const int passes = std::max(1, (bits + 7) / 8);
+  SortCtx cx = w.cx;
+  int64_t* kbuf = w.kbuf;
+  int32_t* vbuf = w.vbuf;
 
   const size_t stage_bytes = (num_slices + 1 + 3 * (size_t)nt) * sizeof(int32_t) + 64;
   HIP_TRY(hipStreamSynchronize(st));
@@ -3341,24 +3345,24 @@ dev_morton_sort(
     o += (bytes + 15) & ~size_t(15);
     return e;
   };
-  HIP_TRY(stage(h_off.data(), h_off.size() * 4, d_pt));
-  HIP_TRY(stage(t_first.data(), nt * 4, cx.tile_first));
-  HIP_TRY(stage(t_count.data(), nt * 4, cx.tile_count));
-  HIP_TRY(stage(t_slice.data(), nt * 4, cx.tile_slice));
+  HIP_TRY(stage(t.off.data(), t.off.size() * 4, w.pt_off));
+  HIP_TRY(stage(t.first.data(), nt * 4, cx.tile_first));
+  HIP_TRY(stage(t.count.data(), nt * 4, cx.tile_count));
+  HIP_TRY(stage(t.slice.data(), nt * 4, cx.tile_slice));
 
   cx.n = n;
   cx.num_tiles = nt;
   cx.num_slices = num_slices;
-  cx.pt_off = d_pt;
+  cx.pt_off = w.pt_off;
   // ping-pong so that the last pass writes the caller's buffers
   int64_t* ka = passes % 2 ? kbuf : (int64_t*)d_morton;
   int32_t* va = passes % 2 ? vbuf : (int32_t*)d_order;
   int64_t* kb = passes % 2 ? (int64_t*)d_morton : kbuf;
   int32_t* vb = passes % 2 ? (int32_t*)d_order : vbuf;
   {
-    Timer t(ctx, "morton_encode");
+    Timer tm(ctx, "morton_encode");
     morton_encode_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-      (const int32_t*)d_xyz, d_pt, num_slices, n, ka, va);
+      (const int32_t*)d_xyz, w.pt_off, num_slices, n, ka, va);
   }
   for (int p = 0; p < passes; p++) {
     cx.key_in = ka;
@@ -3367,15 +3371,15 @@ dev_morton_sort(
     cx.val_out = vb;
     cx.shift = 8 * p;
     {
-      Timer t(ctx, "sort_hist");
+      Timer tm(ctx, "sort_hist");
       sort_hist_kernel<<<std::min(nt, kGridMax), kSortThreads, 0, st>>>(cx);
     }
     {
-      Timer t(ctx, "sort_scan");
+      Timer tm(ctx, "sort_scan");
       sort_scan_kernel<<<1, 1024, 0, st>>>(cx);
     }
     {
-      Timer t(ctx, "sort_scatter");
+      Timer tm(ctx, "sort_scatter");
       sort_scatter_kernel<<<std::min(nt, kGridMax), kSortThreads, 0, st>>>(cx);
     }
     std::swap(ka, kb);
@@ -3383,6 +3387,36 @@ dev_morton_sort(
   }
   HIP_TRY(hipGetLastError());
   return GPCC_OK;
+}
+
+// `bits` significant bits per key; 0: what gpcc_ctx_set_morton_bits said (nothing: all 63)
+static int
+dev_morton_sort(
+  gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const void* d_xyz,
+  void* d_morton, void* d_order, int bits = 0)
+{
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  if (num_slices < 1 || !offsets || offsets[0] != 0 || !d_xyz || !d_morton || !d_order)
+    return fail(GPCC_ERR_INVALID_ARG, "bad arguments");
+  for (int i = 0; i < num_slices; i++)
+    if (offsets[i + 1] <= offsets[i])
+      return fail(GPCC_ERR_INVALID_ARG, "empty or unordered slice");
+  if (offsets[num_slices] > kMaxPoints)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^29 points per batch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (bits <= 0)
+    bits = ctx->morton_bits > 0 ? ctx->morton_bits : 63;
+  const SortTiles tiles = sort_tiles(num_slices, offsets);
+  Arena measure;
+  SortWork work;
+  carve_sort(measure, work, tiles.n(), num_slices, tiles.nt());
+  int rcode = ensure_arena(ctx, measure.used);
+  if (rcode)
+    return rcode;
+  ctx->arena.reset();
+  carve_sort(ctx->arena, work, tiles.n(), num_slices, tiles.nt());
+  return sort_run(ctx, work, bits, tiles, d_xyz, d_morton, d_order);
 }
 
 // the largest coordinate of n positions in host memory; one outside what a Morton code holds is refused
@@ -3423,11 +3457,8 @@ host_morton_sort(
   HIP_TRY(pool.take(N, &d_m));
   HIP_TRY(pool.take(N, &d_o));
   HIP_TRY(h2d_user(ctx, d_x, xyz, sizeof(int32_t) * 3 * n, st));
-  const int saved = ctx->morton_bits;
-  ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)mx));
   const int64_t offs[2] = {0, n};
-  r = dev_morton_sort(ctx, 1, offs, d_x, d_m, d_o);
-  ctx->morton_bits = saved;
+  r = dev_morton_sort(ctx, 1, offs, d_x, d_m, d_o, std::max(1, 3 * bitlen64((uint64_t)mx)));
   if (r)
     return r;
   HIP_TRY(d2h_user(ctx, morton, d_m, sizeof(int64_t) * n, st));
@@ -3526,6 +3557,26 @@ qp_regions_to_points(
 
 // AttributeLods::generate on the device; results stay there.  `extra_bytes`
 // are reserved behind the workspace for the caller (same arena, no regrowth).
+// The stages are lod_levels.hpp's (and lod_scalable.hpp's); what is here is the part that needs the context:
+// checks, the workspace, the transfers and the Morton sorts.
+
+// lod_levels.hpp's host policy
+struct LodHost {
+  gpcc_ctx* ctx;
+  Timer span(const char* name, int level = -1) const { return Timer(ctx, level < 0 ? name : level_name(name, level)); }
+  int grid(int64_t items) const { return grid_for(items, 256); }
+  void launch_subsample(const LodCtx& lc, int ncell) const
+  {
+    // 3 workgroups per CU stay resident (168 registers, no LDS).  One slice
+    // alone takes them all (1 M dense points, the level with the most cells:
+    // 6.4 / 4.5 / 3.85 / 3.8 ms with 256 / 512 / 768 / 1 024 workgroups);
+    // concurrent lanes (run_slices) take 256 each (5 x 1 M points: 9.5-10 ms
+    // per 1 M points from 192 to 768)
+    const int grid = (int)std::min<int64_t>(ctx->lod_grid, ((int64_t)ncell + 255) / 256);
+    lod_subsample_distance_kernel<<<std::max(8, (grid + 7) / 8 * 8), 256, 0, ctx->stream>>>(lc);
+  }
+};
+
 int
 lod_build_core(
   gpcc_ctx* ctx, const gpcc_lod_params* lp, const int32_t* xyz, int32_t n,
@@ -3554,12 +3605,17 @@ lod_build_core(
       return fail(
         GPCC_ERR_UNSUPPORTED,
         "inter prediction together with scalable lifting / canonical point order stays on the reference CPU path");
+  }
+  // the Morton sorts run only as many passes as the codes have bits; positions on the device are not inspected
+  // on the host: there the hint of gpcc_ctx_set_morton_bits bounds the passes (0 = all 63)
+  const int hint_bits = ctx->morton_bits > 0 ? ctx->morton_bits : 63;
+  int frame_bits = hint_bits;
+  if (frame && !frame->on_device) {
     int32_t frame_mx = 0;
-    if (!frame->on_device) {
-      int rf = max_coordinate(frame->xyz, frame->n, &frame_mx, "reference frame coordinate outside [0, 2^21)");
-      if (rf)
-        return rf;
-    }
+    int rf = max_coordinate(frame->xyz, frame->n, &frame_mx, "reference frame coordinate outside [0, 2^21)");
+    if (rf)
+      return rf;
+    frame_bits = std::max(1, 3 * bitlen64((uint64_t)frame_mx));
   }
   const bool scalable = lp->scalable_lifting_enabled_flag != 0;
   if (!scalable && (lp->lod_decimation_type < 0 || lp->lod_decimation_type > 2))
@@ -3572,8 +3628,6 @@ lod_build_core(
     return fail(GPCC_ERR_INVALID_ARG, "num_detail_levels out of range");
   int32_t mx = 0;
   if (xyz_on_device) {
-    // device tier: the positions are not inspected on the host; the Morton-bits
-    // hint bounds the sort's passes (gpcc_ctx_set_morton_bits, 0 = all 63)
     mx = ctx->morton_bits > 0 ? (1 << std::min(21, (ctx->morton_bits + 2) / 3)) - 1 : (1 << 21) - 1;
   } else {
     int rx = max_coordinate(xyz, n, &mx);
@@ -3583,449 +3637,103 @@ lod_build_core(
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
 
-  // Workspace from the context's arena (no allocation per call once it has
-  // grown).  The Morton sort below carves its own scratch from the arena's
-  // start; everything that has to outlive it is placed behind that region.
-  const size_t NF = frame ? (size_t)frame->n : 0;
-  const size_t sort_region = 32 * std::max((size_t)n, NF) + ((size_t)1 << 20);
+  // Workspace from the context's arena (no allocation per call once it has grown): the scratch of the Morton
+  // sorts (of the points, then of the frame), the build's arrays behind it; the caller's bytes follow.  Nothing
+  // below lays the arena out again, so in guard mode the bands live until the next call compares them.
+  const int n_frame = frame ? frame->n : 0;
+  const int n_sort = std::max(n, n_frame);
+  SortWork sort;
+  LodWork w{};
+  auto carve_all = [&](Arena& ar) {
+    carve_sort(ar, sort, n_sort, 1, (n_sort + kSortTile - 1) / kSortTile);
+    lod_carve([&](size_t bytes) { return ar.take<char>(bytes); }, w, n, n_frame, scalable);
+  };
+  Arena measure;
+  carve_all(measure);
+  int rc0 = ensure_arena(ctx, measure.used + extra_bytes);
+  if (rc0)
+    return rc0;
+  Arena& ar = ctx->arena;
+  ar.reset();
+  carve_all(ar);
+  if (ar.used + extra_bytes > ar.cap)
+    return fail(GPCC_ERR_OUT_OF_MEMORY, "arena reservation too small");
+
+  const size_t N = (size_t)n, NF = (size_t)n_frame;
+  if (xyz_on_device)
+    w.xyz = xyz;
+  else if (d_xyz_uploaded)
+    w.xyz = d_xyz_uploaded;
+  else
+    HIP_TRY(h2d_user(ctx, w.xyz_own, xyz, sizeof(int32_t) * 3 * N, st));
+  HIP_TRY(hipMemsetAsync(w.cell_state, 0, sizeof(uint32_t) * 4 * (N + 1), st));
+  HIP_TRY(hipMemsetAsync(w.small, 0, sizeof(int32_t) * 64, st));
+  HIP_TRY(hipMemsetAsync(w.scan, 0, sizeof(unsigned long long) * 1024, st));
+  // Morton order (code, then index)
   {
-    // 26 arrays, the largest 24 B per point (see the DM list below); an inter build adds
-    // the reference frame (positions twice, biased positions, codes, order, list, boxes)
-    // and the flags of the result
-    const size_t mine = (size_t)n * (scalable ? 244 : 232) + 64 * 1024 + (frame ? NF * 56 + (size_t)n * 12 + 64 * 1024 : 0);
-    if (guard_mode())  // a 256-byte band behind every array here and behind the caller's few
-      extra_bytes += 96 * 1024;
-    int rc0 = ensure_arena(ctx, sort_region + mine + extra_bytes);
-    if (rc0)
-      return rc0;
+    const int64_t offs[2] = {0, n};
+    int r = sort_run(ctx, sort, std::max(1, 3 * bitlen64((uint64_t)mx)), sort_tiles(1, offs), w.xyz, w.code, w.order);
+    if (r)
+      return r;
   }
-  size_t ar_used = sort_region;
-  auto dmalloc = [&](size_t bytes) -> void* {
-    const size_t b = (std::max<size_t>(bytes, 256) + 255) & ~size_t(255);
-    if (ar_used + b > ctx->arena.cap)
-      return nullptr;
-    void* p = ctx->arena.base + ar_used;
-    ar_used += b;
-    if (guard_mode()) {  // (Arena::band() for this entry's own carving)
-      if (ar_used + kGuardInner > ctx->arena.cap)
-        return nullptr;
-      ctx->arena.used = ar_used;
-      ctx->arena.band();
-      ar_used = ctx->arena.used;
+  // canonical_point_order_flag / max_points_per_sort_log2_plus1 (PCCTMC3Common.h:2322-2331): the
+  // reference takes the points as they come (or sorts them in chunks).  What the octree geometry
+  // coder hands over IS in (Morton code, index) order -- then neither changes anything and the
+  // build is the one below; any other order stays on the reference CPU path.
+  if (lp->canonical_point_order_flag || lp->max_points_per_sort_log2_plus1) {
+    int32_t moved = 0;
+    lod_count_moved_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, w.order, w.small + kLodMoved);
+    HIP_TRY(hipMemcpyAsync(&moved, w.small + kLodMoved, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (moved)
+      return fail(
+        GPCC_ERR_UNSUPPORTED,
+        "canonical point order / chunked sort with points that are not in Morton order stay on the reference CPU path");
+  }
+  LodHost host{ctx};
+  lod_prepare(lp, w, st, host);
+  const LodFrameParams frame_params{frame ? frame->search_range : 0, frame ? frame->frame_distance : 0};
+  const LodFrameParams* fp = frame ? &frame_params : nullptr;
+  if (frame) {
+    if (frame->on_device) {
+      // the range check is the sticky error word's
+      HIP_TRY(hipMemcpyAsync(w.fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, hipMemcpyDeviceToDevice, st));
+      Timer tm(ctx, "ref_frame_range");
+      ref_frame_range_kernel<<<grid_for((int64_t)(3 * NF), 256), 256, 0, st>>>(w.fxyz, (int64_t)(3 * NF), ctx->d_error);
+    } else {
+      HIP_TRY(h2d_user(ctx, w.fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, st));
     }
-    return p;
-  };
-  auto run = [&]() -> int {
-    const size_t N = (size_t)n;
-    const int nb0 = (n + 31) >> 5, nb1 = (nb0 + 31) >> 5, nb2 = (nb1 + 31) >> 5;
-#define DM(type, name, count)                                   \
-  type* name = (type*)dmalloc(sizeof(type) * (count));          \
-  if (!name)                                                    \
-    return fail(GPCC_ERR_OUT_OF_MEMORY, "hipMalloc(" #name ")");
-    DM(int32_t, d_xyz_own, 3 * N)
-    const int32_t* d_xyz = xyz_on_device ? xyz : d_xyz_uploaded ? d_xyz_uploaded : d_xyz_own;
-    DM(int64_t, d_code, N)
-    DM(int32_t, d_order, N)
-    DM(int32_t, d_pos, 3 * N)
-    DM(int32_t, d_bpos, 3 * N)
-    DM(int32_t, d_list_a, N + 1)
-    DM(int32_t, d_list_b, N + 1)
-    DM(int32_t, d_refine, N + 1)
-    DM(uint8_t, d_flags, N + 1)
-    DM(uint8_t, d_heads, N + 1)
-    DM(int32_t, d_positions, N + 1)
-    DM(int32_t, d_cell_first, N + 2)
-    DM(int32_t, d_cent_tmp, N + 2)
-    DM(int64_t, d_cell_key, N + 1)
-    DM(int64_t, d_ret_key, N + 1)
-    DM(uint32_t, d_cell_state, 4 * (N + 1))
-    DM(int32_t, d_small, 64)  // ticket[8], error, counts[2]
-    DM(unsigned long long, d_scan, 1024)
-    DM(long long, d_atlas_limit, 1)
-    DM(int32_t, d_box, (size_t)2 * 2 * 3 * (nb0 + nb1 + nb2 + 3))
-    DM(int32_t, d_pred_count, N)
-    DM(int32_t, d_pred_point, 3 * N)
-    DM(uint64_t, d_pred_dist2, 3 * N)
-    DM(int32_t, d_pt2pred, N)
-    DM(int32_t, d_indexes, N)
-    DM(int32_t, d_neigh_index, 3 * N)
-    DM(int32_t, d_weight, 3 * N)
-    DM(int32_t, d_bpos_lod, scalable ? 3 * N : 1)
-    // attribute inter prediction: the reference frame, sorted
-    const int nfb0 = ((int)NF + 31) >> 5, nfb1 = (nfb0 + 31) >> 5, nfb2 = (nfb1 + 31) >> 5;
-    DM(int32_t, d_fxyz, 3 * NF + 1)
-    DM(int64_t, d_fcode, NF + 1)
-    DM(int32_t, d_forder, NF + 1)
-    DM(int32_t, d_fpos, 3 * NF + 1)
-    DM(int32_t, d_fbpos, 3 * NF + 1)
-    DM(int32_t, d_flist, NF + 1)
-    DM(int32_t, d_fbox, (size_t)2 * 3 * (nfb0 + nfb1 + nfb2 + 3) + 1)
-    DM(int32_t, d_inter_ref, frame ? 3 * N : 1)
-#undef DM
-    int32_t* d_ticket = d_small;
-    int32_t* d_error = d_small + 8;
-    int32_t* d_counts = d_small + 16;
-    if (!xyz_on_device && !d_xyz_uploaded)
-      HIP_TRY(h2d_user(ctx, d_xyz_own, xyz, sizeof(int32_t) * 3 * N, st));
-    HIP_TRY(hipMemsetAsync(d_cell_state, 0, sizeof(uint32_t) * 4 * (N + 1), st));
-    HIP_TRY(hipMemsetAsync(d_small, 0, sizeof(int32_t) * 64, st));
-    HIP_TRY(hipMemsetAsync(d_scan, 0, sizeof(unsigned long long) * 1024, st));
-    // Morton order (code, then index)
-    {
-      const int saved = ctx->morton_bits;
-      ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)mx));
-      const int64_t offs[2] = {0, n};
-      int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_code, d_order);
-      ctx->morton_bits = saved;
-      if (r)
-        return r;
-    }
-    // canonical_point_order_flag / max_points_per_sort_log2_plus1 (PCCTMC3Common.h:2322-2331): the
-    // reference takes the points as they come (or sorts them in chunks).  What the octree geometry
-    // coder hands over IS in (Morton code, index) order -- then neither changes anything and the
-    // build is the one below; any other order stays on the reference CPU path.
-    if (lp->canonical_point_order_flag || lp->max_points_per_sort_log2_plus1) {
-      int32_t moved = 0;
-      lod_count_moved_kernel<<<grid_for(n, 256), 256, 0, st>>>(n, d_order, d_small + 24);
-      HIP_TRY(hipMemcpyAsync(&moved, d_small + 24, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (moved)
-        return fail(
-          GPCC_ERR_UNSUPPORTED,
-          "canonical point order / chunked sort with points that are not in Morton order stay on the reference CPU path");
-    }
-    {
-      Timer tm(ctx, "lod_gather");
-      lod_gather_pos_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-        n, d_xyz, d_order, lp->lod_neigh_bias[0], lp->lod_neigh_bias[1],
-        lp->lod_neigh_bias[2], d_pos, d_bpos, d_list_a);
-    }
-    // the reference frame of inter prediction: Morton order, biased positions, the list
-    // 0, 1, 2, ... and one box hierarchy over it (buildPredictorsFast :2352-2376,
-    // computeNearestNeighbors :1270-1292) -- the same at every level of detail
-    int32_t* fbox[3][2] = {};
-    if (frame) {
-      const int saved = ctx->morton_bits;
-      if (frame->on_device) {
-        // the range check is the sticky error word's; the Morton-bits hint bounds the sort's passes as it does for
-        // the slice's own positions
-        HIP_TRY(hipMemcpyAsync(d_fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, hipMemcpyDeviceToDevice, st));
-        Timer tm(ctx, "ref_frame_range");
-        ref_frame_range_kernel<<<grid_for((int64_t)(3 * NF), 256), 256, 0, st>>>(d_fxyz, (int64_t)(3 * NF), ctx->d_error);
-      } else {
-        HIP_TRY(h2d_user(ctx, d_fxyz, frame->xyz, sizeof(int32_t) * 3 * NF, st));
-        int32_t fmx = 0;
-        for (size_t i = 0; i < 3 * NF; i++)
-          fmx = std::max(fmx, frame->xyz[i]);
-        ctx->morton_bits = std::max(1, 3 * bitlen64((uint64_t)fmx));
-      }
-      const int64_t offs[2] = {0, (int64_t)NF};
-      int r = dev_morton_sort(ctx, 1, offs, d_fxyz, d_fcode, d_forder);
-      ctx->morton_bits = saved;
-      if (r)
-        return r;
-      lod_gather_pos_kernel<<<grid_for((int64_t)NF, 256), 256, 0, st>>>(
-        (int)NF, d_fxyz, d_forder, lp->lod_neigh_bias[0], lp->lod_neigh_bias[1],
-        lp->lod_neigh_bias[2], d_fpos, d_fbpos, d_flist);
-      {
-        int32_t* p = d_fbox;
-        const int cnt[3] = {nfb0 + 1, nfb1 + 1, nfb2 + 1};
-        for (int lev = 0; lev < 3; lev++)
-          for (int m = 0; m < 2; m++) {
-            fbox[lev][m] = p;
-            p += 3 * cnt[lev];
-          }
-      }
-      lod_box0_kernel<<<grid_for(std::max(nfb0, 1), 256), 256, 0, st>>>(
-        (int)NF, d_flist, d_fbpos, fbox[0][0], fbox[0][1]);
-      lod_box_up_kernel<<<grid_for(std::max(nfb1, 1), 256), 256, 0, st>>>(
-        nfb0, fbox[0][0], fbox[0][1], fbox[1][0], fbox[1][1]);
-      lod_box_up_kernel<<<1, 256, 0, st>>>(nfb1, fbox[1][0], fbox[1][1], fbox[2][0], fbox[2][1]);
-      HIP_TRY(hipGetLastError());
-    }
-
-    // box storage: [list 0 = retained, 1 = refine][level][min/max]
-    int32_t* box[2][3][2];
-    {
-      int32_t* p = d_box;
-      const int cnt[3] = {nb0 + 1, nb1 + 1, nb2 + 1};
-      for (int l = 0; l < 2; l++)
-        for (int lev = 0; lev < 3; lev++)
-          for (int m = 0; m < 2; m++) {
-            box[l][lev][m] = p;
-            p += 3 * cnt[lev];
-          }
-    }
-    auto build_boxes = [&](int which, const int32_t* list, int cnt) {
-      const int c0 = (cnt + 31) >> 5, c1 = (c0 + 31) >> 5;
-      {
-        Timer tm(ctx, "lod_boxes");
-        lod_box0_kernel<<<grid_for(std::max(c0, 1), 256), 256, 0, st>>>(
-          cnt, list, d_bpos, box[which][0][0], box[which][0][1]);
-      }
-      {
-        Timer tm(ctx, "lod_boxes");
-        lod_box_up_kernel<<<grid_for(std::max(c1, 1), 256), 256, 0, st>>>(
-          c0, box[which][0][0], box[which][0][1], box[which][1][0], box[which][1][1]);
-      }
-      {
-        Timer tm(ctx, "lod_boxes");
-        lod_box_up_kernel<<<1, 256, 0, st>>>(
-          c1, box[which][1][0], box[which][1][1], box[which][2][0], box[which][2][1]);
-      }
-    };
-
-    int scan_epoch = 0;
-    auto partition = [&](int cnt, const uint8_t* flags, const int32_t* list,
-                         int32_t* out_true, int32_t* out_false, int* n_true) -> int {
-      scan_epoch++;
-      const int grid = (int)std::min<int64_t>(1024, ((int64_t)cnt + 1023) / 1024);
-      {
-        Timer tm(ctx, "lod_partition");
-        lod_partition_kernel<<<std::max(grid, 1), 256, 0, st>>>(
-          cnt, flags, list, out_true, out_false, d_counts, d_scan, scan_epoch);
-      }
-      int32_t h = 0;
-      HIP_TRY(hipMemcpyAsync(&h, d_counts, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      *n_true = h;
-      return GPCC_OK;
-    };
-
-    std::vector<int32_t> npl;
-    npl.push_back(n);
-    int32_t* d_input = d_list_a;
-    int32_t* d_ret = d_list_b;
-    int n_in = n, n_idx = 0;
-    if (scalable) {
-      // its own level loop (lod_scalable.hpp), same kernels
-      LodWork w{};
-      w.n = n;
-      w.code = d_code;
-      w.order = d_order;
-      w.pos = d_pos;
-      w.bpos = d_bpos;
-      w.bpos_lod = d_bpos_lod;
-      w.list_a = d_list_a;
-      w.list_b = d_list_b;
-      w.refine = d_refine;
-      w.flags = d_flags;
-      w.heads = d_heads;
-      w.nxt0 = d_cell_first;
-      w.nj0 = d_positions;
-      w.nj1 = d_cent_tmp;
-      w.ret_key = d_ret_key;
-      w.counts = d_counts;
-      w.scan = d_scan;
-      w.atlas_limit = d_atlas_limit;
-      for (int l = 0; l < 2; l++)
-        for (int lev = 0; lev < 3; lev++)
-          for (int m = 0; m < 2; m++)
-            w.box[l][lev][m] = box[l][lev][m];
-      w.pred_count = d_pred_count;
-      w.pred_point = d_pred_point;
-      w.pred_dist2 = d_pred_dist2;
-      w.pt2pred = d_pt2pred;
-      w.indexes = d_indexes;
-      Timer tm(ctx, "lod_scalable_levels");
-      HIP_TRY(lod_scalable_levels(
-        lp, w, st, &npl, &scan_epoch, partial ? partial->first_level : 0,
-        partial ? partial->geom_num_points - n : 0));
-      n_in = 0;  // the loop below has nothing left to do
-    }
-    for (int lod = 0; n_in > 0 && lod < max_levels; lod++) {
-      const int start = n_idx;
-      int n_ret = 0, n_ref = 0;
-      const int shift_bits0 = lp->dist2 + lp->attr_dist2_delta + lod;
-      if (lod == max_levels - 1 || (lp->lod_decimation_type != 1 && n_in == 1)) {
-        HIP_TRY(hipMemcpyAsync(
-          d_refine + start, d_input, sizeof(int32_t) * n_in, hipMemcpyDeviceToDevice, st));
-        n_ref = n_in;
-      } else {
-        if (lp->lod_decimation_type == 1) {
-          const int period = lp->lod_sampling_period[lod];
-          if (period < 1)
-            return fail(GPCC_ERR_INVALID_ARG, "lod_sampling_period < 1");
-          lod_flag_periodic_kernel<<<grid_for(n_in, 256), 256, 0, st>>>(n_in, period, d_flags);
-        } else if (lp->lod_decimation_type == 2) {
-          const int period = lp->lod_sampling_period[lod];
-          if (period < 1)
-            return fail(GPCC_ERR_INVALID_ARG, "lod_sampling_period < 1");
-          LodCtx lc{};
-          lc.code = d_code;
-          lc.pos = d_pos;
-          lc.input = d_input;
-          lc.n_in = n_in;
-          lc.shift3 = 3 * (shift_bits0 + 1);
-          lc.flags = d_flags;
-          // group starts = orbit of 0 under next(): pointer doubling
-          int32_t* nxt0 = d_cell_first;               // [n_in + 1]
-          int32_t* nj[2] = {d_positions, d_cent_tmp};  // squared pointers
-          Timer tm(ctx, "lod_centroid");
-          lod_centroid_next_kernel<<<grid_for(n_in + 1, 256), 256, 0, st>>>(lc, period, nxt0);
-          HIP_TRY(hipMemsetAsync(d_heads, 0, (size_t)n_in + 1, st));
-          HIP_TRY(hipMemsetAsync(d_heads, 1, 1, st));
-          const int32_t* cur = nxt0;
-          for (int r = 0, reach = 1; reach < n_in; r++, reach *= 2) {
-            lod_centroid_jump_kernel<<<grid_for(n_in + 1, 256), 256, 0, st>>>(
-              n_in, cur, nj[r & 1], d_heads);
-            cur = nj[r & 1];
-          }
-          lod_centroid_pick_kernel<<<grid_for(n_in, 256), 256, 0, st>>>(
-            lc, shift_bits0, nxt0, d_heads, 1);
-        } else {
-          LodCtx lc{};
-          lc.n = n;
-          lc.code = d_code;
-          lc.order = d_order;
-          lc.pos = d_pos;
-          lc.bpos = d_bpos;
-          lc.input = d_input;
-          lc.n_in = n_in;
-          lc.shift3 = 3 * (shift_bits0 + 1);
-          lc.boundary = std::min(63, lc.shift3 + 21);
-          lc.radius2 = (int64_t)3 << (shift_bits0 << 1);
-          lc.cell_first = d_cell_first;
-          lc.cell_key = d_cell_key;
-          lc.cell_state = d_cell_state;
-          lc.ticket = d_ticket;
-          lc.error = d_error;
-          lc.epoch = lod + 1;
-          lc.flags = d_flags;
-          {
-            Timer tm(ctx, "lod_cell_heads");
-            lod_flag_cell_heads_kernel<<<grid_for(n_in, 256), 256, 0, st>>>(lc, d_heads, d_positions);
-          }
-          int ncell = 0;
-          int r = partition(n_in, d_heads, d_positions, d_cell_first, nullptr, &ncell);
-          if (r)
-            return r;
-          HIP_TRY(hipMemcpyAsync(
-            d_cell_first + ncell, &n_in, sizeof(int32_t), hipMemcpyHostToDevice, st));
-          HIP_TRY(hipMemsetAsync(d_ticket, 0, sizeof(int32_t) * 8, st));
-          lc.ncell = ncell;
-          lod_cell_keys_kernel<<<grid_for(ncell, 256), 256, 0, st>>>(lc);
-          // 3 workgroups per CU stay resident (168 registers, no LDS).  One slice
-          // alone takes them all (1 M dense points, the level with the most cells:
-          // 6.4 / 4.5 / 3.85 / 3.8 ms with 256 / 512 / 768 / 1 024 workgroups);
-          // concurrent lanes (run_slices) take 256 each (5 x 1 M points: 9.5-10 ms
-          // per 1 M points from 192 to 768)
-          const int grid = (int)std::min<int64_t>(ctx->lod_grid, ((int64_t)ncell + 255) / 256);
-          {
-            Timer tm(ctx, level_name("lod_subsample", lod));
-            lod_subsample_distance_kernel<<<std::max(8, (grid + 7) / 8 * 8), 256, 0, st>>>(lc);
-          }
-        }
-        int r = partition(n_in, d_flags, d_input, d_ret, d_refine + start, &n_ret);
-        if (r)
-          return r;
-        n_ref = n_in - n_ret;
-      }
-      n_idx += n_ref;
-
-      // nearest neighbours of this LoD's refinement points
-      if (n_ref > 0) {
-        NnCtx nc{};
-        nc.n = n;
-        nc.code = d_code;
-        nc.order = d_order;
-        nc.bpos = d_bpos;
-        nc.retained = d_ret;
-        nc.ret_key = d_ret_key;
-        nc.n_ret = n_ret;
-        nc.refine = d_refine + start;
-        nc.n_ref = n_ref;
-        nc.start = start;
-        nc.shift3 = 3 * (1 + shift_bits0);
-        nc.boundary = std::min(63, nc.shift3 + 21);
-        nc.distribution = lp->prediction_with_distribution_enabled;
-        nc.range_inter = frame ? frame->search_range : lp->inter_lod_search_range;
-        nc.range_intra = frame ? frame->search_range : lp->intra_lod_search_range;
-        nc.intra = lod >= lp->intra_lod_prediction_skip_layers;
-        if (frame) {
-          nc.frame_code = d_fcode;
-          nc.frame_order = d_forder;
-          nc.frame_bpos = d_fbpos;
-          nc.frame_identity = d_flist;
-          nc.n_frame = (int)NF;
-          nc.frame_range = frame->search_range;
-          nc.frame_boundary = std::min(63, nc.shift3 + 9);
-          for (int lev = 0; lev < 3; lev++)
-            for (int m = 0; m < 2; m++)
-              nc.box_frame[lev][m] = fbox[lev][m];
-        }
-        nc.max_neigh = lp->num_pred_nearest_neighbours_minus1 + 1;
-        for (int lev = 0; lev < 3; lev++)
-          for (int m = 0; m < 2; m++) {
-            nc.box_ret[lev][m] = box[0][lev][m];
-            nc.box_ref[lev][m] = box[1][lev][m];
-          }
-        nc.atlas_limit = d_atlas_limit;
-        nc.pred_count = d_pred_count;
-        nc.pred_point = d_pred_point;
-        nc.pred_dist2 = d_pred_dist2;
-        nc.pt2pred = d_pt2pred;
-        nc.indexes = d_indexes;
-        if (n_ret > 0) {
-          lod_ret_keys_kernel<<<grid_for(n_ret, 256), 256, 0, st>>>(
-            n_ret, d_ret, d_code, nc.shift3, d_ret_key);
-          build_boxes(0, d_ret, n_ret);
-        }
-        if (nc.intra)
-          build_boxes(1, d_refine + start, n_ref);
-        const long long inf = INT64_MAX;
-        HIP_TRY(hipMemcpyAsync(d_atlas_limit, &inf, sizeof(inf), hipMemcpyHostToDevice, st));
-        if (n_ret > 0)
-          {
-            Timer tm(ctx, "lod_atlas_limit");
-            lod_atlas_limit_kernel<<<grid_for(n_ret, 256), 256, 0, st>>>(nc, d_atlas_limit);
-          }
-        {
-          Timer tm(ctx, level_name("lod_nn_search", lod));
-          if (frame)
-            lod_nn_search_kernel<false, true><<<grid_for(n_ref, 256), 256, 0, st>>>(nc);
-          else
-            lod_nn_search_kernel<false><<<grid_for(n_ref, 256), 256, 0, st>>>(nc);
-        }
-      }
-      if (n_ret > 0)
-        npl.push_back(n_ret);
-      std::swap(d_input, d_ret);
-      n_in = n_ret;
-    }
-    {
-      Timer tm(ctx, "lod_finalise");
-      if (frame)
-        lod_finalise_inter_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-          n, d_pred_count, d_pred_point, d_pt2pred, d_pred_dist2, d_neigh_index, d_inter_ref,
-          frame->frame_distance);
-      else
-        lod_finalise_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-          n, 0, d_pred_count, d_pred_point, d_pt2pred, d_pred_dist2, d_neigh_index);
-    }
-    lod_compute_weights_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-      n, d_pred_count, d_pred_dist2, d_weight);
-    if (lp->attr_encoding == 1 && lp->pred_weight_blending_enabled_flag) {
-      if (frame)
-        lod_blend_weights_inter_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-          n, d_pred_count, d_pred_point, d_xyz, d_fxyz, d_weight);
-      else
-        lod_blend_weights_kernel<<<grid_for(n, 256), 256, 0, st>>>(
-          n, d_pred_count, d_pred_point, d_xyz, d_weight);
-    }
+    const int64_t offs[2] = {0, (int64_t)NF};
+    int r = sort_run(ctx, sort, frame_bits, sort_tiles(1, offs), w.fxyz, w.fcode, w.forder);
+    if (r)
+      return r;
+    lod_prepare_frame(lp, w, st, host);
     HIP_TRY(hipGetLastError());
-    out->count = d_pred_count;
-    out->xyz = d_xyz;
-    out->neigh_index = d_neigh_index;
-    out->weight = d_weight;
-    out->indexes = d_indexes;
-    out->error = d_error;
-    out->inter_ref = frame ? d_inter_ref : nullptr;
-    out->npl.assign(npl.rbegin(), npl.rend());
-    out->arena_end = ar_used;
-    return GPCC_OK;
-  };
-  return run();
+  }
+
+  std::vector<int32_t> npl;
+  int scan_epoch = 0;
+  if (scalable) {
+    Timer tm(ctx, "lod_scalable_levels");
+    HIP_TRY(lod_scalable_levels(
+      lp, w, st, &npl, &scan_epoch, partial ? partial->first_level : 0,
+      partial ? partial->geom_num_points - n : 0));
+  } else {
+    HIP_TRY(lod_plain_levels(lp, w, fp, st, &npl, &scan_epoch, host));
+    if (npl.empty())
+      return fail(GPCC_ERR_INVALID_ARG, "lod_sampling_period < 1");
+  }
+  HIP_TRY(lod_finish(lp, w, fp, st, host));
+  out->count = w.pred_count;
+  out->xyz = w.xyz;
+  out->neigh_index = w.neigh_index;
+  out->weight = w.weight;
+  out->indexes = w.indexes;
+  out->error = w.small + kLodError;
+  out->inter_ref = frame ? w.inter_ref : nullptr;
+  out->npl.assign(npl.rbegin(), npl.rend());
+  out->arena_end = ar.used;
+  return GPCC_OK;
 }
 
 int
@@ -4036,6 +3744,29 @@ lod_error_word(gpcc_ctx* ctx, const LodDeviceOut& o)
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (h_err)
     return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
+  return GPCC_OK;
+}
+
+// the structure into the caller's memory (inter_ref: inter builds)
+int
+lod_download(
+  gpcc_ctx* ctx, const LodDeviceOut& o, int32_t n, int32_t* neigh_count, int32_t* neigh_index,
+  int32_t* neigh_weight, int32_t* indexes, int32_t* num_points_in_lod, int32_t* num_lods, int32_t* inter_ref)
+{
+  hipStream_t st = ctx->stream;
+  const size_t N = (size_t)n;
+  HIP_TRY(d2h_user(ctx, neigh_count, o.count, sizeof(int32_t) * N, st));
+  HIP_TRY(d2h_user(ctx, neigh_index, o.neigh_index, sizeof(int32_t) * 3 * N, st));
+  HIP_TRY(d2h_user(ctx, neigh_weight, o.weight, sizeof(int32_t) * 3 * N, st));
+  HIP_TRY(d2h_user(ctx, indexes, o.indexes, sizeof(int32_t) * N, st));
+  if (inter_ref)
+    HIP_TRY(d2h_user(ctx, inter_ref, o.inter_ref, sizeof(int32_t) * 3 * N, st));
+  int r = lod_error_word(ctx, o);
+  if (r)
+    return r;
+  *num_lods = (int)o.npl.size();
+  for (size_t i = 0; i < o.npl.size(); i++)
+    num_points_in_lod[i] = o.npl[i];
   return GPCC_OK;
 }
 
@@ -4052,21 +3783,7 @@ lod_build(
   int r = lod_build_core(ctx, lp, xyz, n, 0, &o, false, nullptr, partial);
   if (r)
     return r;
-  hipStream_t st = ctx->stream;
-  const size_t N = (size_t)n;
-  int32_t h_err = 0;
-  HIP_TRY(d2h_user(ctx, neigh_count, o.count, sizeof(int32_t) * N, st));
-  HIP_TRY(d2h_user(ctx, neigh_index, o.neigh_index, sizeof(int32_t) * 3 * N, st));
-  HIP_TRY(d2h_user(ctx, neigh_weight, o.weight, sizeof(int32_t) * 3 * N, st));
-  HIP_TRY(d2h_user(ctx, indexes, o.indexes, sizeof(int32_t) * N, st));
-  HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h_err)
-    return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
-  *num_lods = (int)o.npl.size();
-  for (size_t i = 0; i < o.npl.size(); i++)
-    num_points_in_lod[i] = o.npl[i];
-  return GPCC_OK;
+  return lod_download(ctx, o, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods, nullptr);
 }
 
 int
@@ -4083,22 +3800,8 @@ lod_build_inter(
   int r = lod_build_core(ctx, lp, xyz, n, 0, &o, false, &frame);
   if (r)
     return r;
-  hipStream_t st = ctx->stream;
-  const size_t N = (size_t)n;
-  int32_t h_err = 0;
-  HIP_TRY(d2h_user(ctx, neigh_count, o.count, sizeof(int32_t) * N, st));
-  HIP_TRY(d2h_user(ctx, neigh_index, o.neigh_index, sizeof(int32_t) * 3 * N, st));
-  HIP_TRY(d2h_user(ctx, neigh_weight, o.weight, sizeof(int32_t) * 3 * N, st));
-  HIP_TRY(d2h_user(ctx, indexes, o.indexes, sizeof(int32_t) * N, st));
-  HIP_TRY(d2h_user(ctx, inter_ref, o.inter_ref, sizeof(int32_t) * 3 * N, st));
-  HIP_TRY(hipMemcpyAsync(&h_err, o.error, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h_err)
-    return fail(GPCC_ERR_HIP, "a dependency wait in the LoD sub-sampling kernel expired");
-  *num_lods = (int)o.npl.size();
-  for (size_t i = 0; i < o.npl.size(); i++)
-    num_points_in_lod[i] = o.npl[i];
-  return GPCC_OK;
+  return lod_download(
+    ctx, o, n, neigh_count, neigh_index, neigh_weight, indexes, num_points_in_lod, num_lods, inter_ref);
 }
 
 // ---- one slice over a structure that lod_build_core left on the device -----------------------
@@ -4533,10 +4236,7 @@ slice_driver(
   const int bits = std::max(1, 3 * bitlen64((uint64_t)mx));
   const int64_t offs[2] = {0, n};
   {
-    const int saved = ctx->morton_bits;
-    ctx->morton_bits = bits;
-    int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_m, d_order);
-    ctx->morton_bits = saved;
+    int r = dev_morton_sort(ctx, 1, offs, d_xyz, d_m, d_order, bits);
     if (r)
       return r;
   }

@@ -1,5 +1,5 @@
-"""ctypes loader of tests/emu/liblod_emu.so (TEST INFRASTRUCTURE): the scalable-lifting LoD build
-of the library (lod_scalable.hpp + lod_kernels.hpp) compiled for the CPU wavefront emulator."""
+"""ctypes loader of tests/emu/liblod_emu.so (TEST INFRASTRUCTURE): the LoD builds of the library
+(lod_levels.hpp, lod_scalable.hpp + lod_kernels.hpp) compiled for the CPU wavefront emulator."""
 import ctypes as C
 import os
 import subprocess

@@ -28,7 +28,8 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     deps = SRCS + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith(("lod_", "lift_"))]
-    deps += [os.path.join(ROOT, "include", "gpcc_attr_mi355.h"), os.path.join(EMU_DIR, "hip", "hip_runtime.h")]
+    deps += [os.path.join(ROOT, "include", "gpcc_attr_mi355.h"), os.path.join(EMU_DIR, "hip", "hip_runtime.h"),
+             os.path.join(EMU_DIR, "lod_emu_blocks.hpp")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1221,8 +1221,9 @@ int gpcc_recolour(
  * outside 1 .. GPCC_RC_MAX_ATTRS, a c other than 1 or 3, a bit depth outside 1 .. 16, a null
  * pointer, two attributes whose output buffers overlap.  On any failure no output buffer is
  * written, the pooled blocks are back in the pool and the context works afterwards.  Host tier,
- * synchronous: the results come down behind the last kernel, one wait at the end.  There is no
- * device tier and gpcc_ctx_reserve does not cover the workspace. */
+ * synchronous: the results come down behind the last kernel, one wait at the end.  The device
+ * tier, for a batch of slices per call, is gpcc_dev_recolour_attrs; gpcc_ctx_reserve does not
+ * cover the workspace. */
 #define GPCC_RC_MAX_ATTRS 4
 typedef struct gpcc_recolour_attr {
   const int32_t* src;   /* [ns][c], values 0 .. 65535 */
@@ -1235,6 +1236,50 @@ int gpcc_recolour_attrs(
   gpcc_ctx* ctx, const gpcc_recolour_params* params, const int32_t* src_xyz, int32_t ns,
   const int32_t* tgt_xyz, int32_t nt, const gpcc_recolour_attr* attrs, int32_t num_attrs,
   float source_to_target_scale, const int32_t target_to_source_offset[3]);
+
+/* Device tier: every attribute of a BATCH of slices in one call, everything resident in HBM -- no
+ * position and no attribute crosses PCIe.  Slice s recolours the targets [tgt_offsets[s],
+ * tgt_offsets[s + 1]) from the sources [src_offsets[s], src_offsets[s + 1]) of the concatenated
+ * arrays: the layout gpcc_src_partition produces as out_offsets and the device-tier coders take as
+ * offsets; d_tgt is what gpcc_dev_*_encode_attr take as d_attrs.  For every slice and attribute the
+ * output equals what gpcc_recolour_attrs gives for that slice alone, equidistant candidates
+ * included; a slice's result does not depend on its neighbours in the batch.
+ * The k-d trees of all slices are built as two FORESTS (the sources', the targets'): root r is slice
+ * r's tree, all nodes of a level of all trees are split by the same launches, and the host waits on
+ * the stream once per level as the host tier does -- neither the launches of any stage nor the waits
+ * depend on num_slices.  Per slice, as in the reference: target_to_source_offsets[s], the point
+ * counts in the error weights, and under a finite max_geometry_dist2_fwd the first limited target
+ * (a limited target shrinks the results of the later targets of ITS slice only).
+ * Everything behind the trees is enqueued and the call returns: results are valid after
+ * gpcc_ctx_synchronize.  Workspace comes from the context's pool as in the host tier;
+ * gpcc_ctx_reserve is NOT extended to it (the first call of a shape allocates).
+ * GPCC_ERR_INVALID_ARG, on the host from the offsets and ahead of any launch: everything
+ * gpcc_recolour_attrs refuses; offsets that do not ascend from 0 or totals above 2^27; a slice that
+ * is empty on one side only (a slice empty on BOTH sides is allowed and skipped); two attributes
+ * whose d_tgt ranges overlap, or a d_tgt that is a d_src.  GPCC_ERR_UNSUPPORTED for the call: a
+ * non-empty slice with fewer sources than num_neighbours_fwd or fewer targets than
+ * num_neighbours_bwd; a tree of any slice deeper than 64 levels.  The slices' bounding boxes are
+ * looked at at the build's first wait: a coordinate outside (-2^30, 2^30) is GPCC_ERR_INVALID_ARG.
+ * In every failing case no byte of any d_tgt has been written, the pooled blocks are back in the
+ * pool and the context works afterwards.
+ * Not part of this entry: a device tier of gpcc_quantize_positions / gpcc_src_partition (the caller
+ * uploads the partitioned source once, in gpcc_src_partition's layout), the multi tier,
+ * gpcc_ctx_reserve, a shim TU (recolouring has no link seam), the per-level host wait (it stays),
+ * and the host-tier entries, which are not re-expressed through the forest. */
+typedef struct gpcc_dev_recolour_attr {
+  const void* d_src;  /* int32 [src_offsets[S]][c], values 0 .. 65535, slices back to back */
+  void* d_tgt;        /* int32 [tgt_offsets[S]][c] out: the layout gpcc_dev_*_encode_attr take as d_attrs */
+  int32_t c;          /* 1 or 3 */
+  int32_t bitdepth;   /* 1 .. 16 */
+} gpcc_dev_recolour_attr;
+
+int gpcc_dev_recolour_attrs(
+  gpcc_ctx* ctx, const gpcc_recolour_params* params, int32_t num_slices,
+  const int64_t* src_offsets, const void* d_src_xyz,   /* host [S+1]; device int32 [.][3] */
+  const int64_t* tgt_offsets, const void* d_tgt_xyz,   /* host [S+1]; device int32 [.][3] */
+  const gpcc_dev_recolour_attr* attrs, int32_t num_attrs,   /* 1 .. GPCC_RC_MAX_ATTRS */
+  float source_to_target_scale,
+  const int32_t* target_to_source_offsets);            /* host [S][3]: _originInCodingCoords + _sliceOrigin per slice */
 
 /* ------------------------------------------------------------------ */
 /* unique-position quantisation and source partitions                   */

@@ -9,7 +9,7 @@ from .params import (LiftParams, LodParams, PredParams, RahtInterParams, RahtPar
                      lod_params, pred_params, raht_params, recolour_params)
 from .params import SphericalParams, spherical_params  # noqa: F401
 from .params import QuantizeParams, quantize_params  # noqa: F401
-from .params import GPCC_RC_MAX_ATTRS, RecolourAttr  # noqa: F401
+from .params import GPCC_RC_MAX_ATTRS, DevRecolourAttr, RecolourAttr  # noqa: F401
 
 
 def context(device=0, stream=None):

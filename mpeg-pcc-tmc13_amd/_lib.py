@@ -3,7 +3,8 @@ if the HIP library is missing or a call fails this module raises."""
 import ctypes as C
 import os
 
-from .params import LiftParams, LodParams, PredParams, QuantizeParams, RahtParams, RecolourAttr, SphericalParams
+from .params import (DevRecolourAttr, LiftParams, LodParams, PredParams, QuantizeParams, RahtParams, RecolourAttr,
+                     SphericalParams)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GPCC_LIB_PATH: an experiment build of the same library (tools/, parameter sweeps)
@@ -21,7 +22,7 @@ ABI_SYMBOLS = [
     "gpcc_raht_forward_inter", "gpcc_raht_inverse_inter",
     "gpcc_dev_raht_forward", "gpcc_dev_raht_inverse", "gpcc_dev_attr_morton_sort",
     "gpcc_ctx_set_profiling", "gpcc_ctx_kernel_times", "gpcc_ctx_stats",
-    "gpcc_lift_forward", "gpcc_lift_inverse", "gpcc_lod_compute_weights", "gpcc_lod_build", "gpcc_lod_build_inter", "gpcc_lift_forward_inter", "gpcc_lift_inverse_inter", "gpcc_pred_forward_inter", "gpcc_pred_inverse_inter", "gpcc_estimate_dist2", "gpcc_recolour", "gpcc_recolour_attrs", "gpcc_raht_encode_attr", "gpcc_raht_decode_attr",
+    "gpcc_lift_forward", "gpcc_lift_inverse", "gpcc_lod_compute_weights", "gpcc_lod_build", "gpcc_lod_build_inter", "gpcc_lift_forward_inter", "gpcc_lift_inverse_inter", "gpcc_pred_forward_inter", "gpcc_pred_inverse_inter", "gpcc_estimate_dist2", "gpcc_recolour", "gpcc_recolour_attrs", "gpcc_dev_recolour_attrs", "gpcc_raht_encode_attr", "gpcc_raht_decode_attr",
     "gpcc_lift_encode_attr", "gpcc_lift_decode_attr", "gpcc_zero_run_pack", "gpcc_raht_encode_attr_packed",
     "gpcc_raht_encode_attr_packed_regions", "gpcc_raht_decode_attr_regions",
     "gpcc_dev_lod_build", "gpcc_dev_lift_encode_attr", "gpcc_dev_lift_decode_attr",
@@ -141,6 +142,8 @@ def load():
     lib.gpcc_estimate_dist2.argtypes = [vp, vp, i32, i32, i32, C.c_float, C.POINTER(i32)]
     lib.gpcc_recolour.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, C.c_float, C.POINTER(i32), vp]
     lib.gpcc_recolour_attrs.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(RecolourAttr), i32, C.c_float, C.POINTER(i32)]
+    lib.gpcc_dev_recolour_attrs.argtypes = [vp, vp, i32, i64p, vp, i64p, vp, C.POINTER(DevRecolourAttr), i32, C.c_float,
+                                            C.POINTER(i32)]
     lib.gpcc_dev_lod_build.argtypes = [vp, C.POINTER(LodParams), i32, i64p, vp, vp, vp, vp, vp, vp, vp]
     for name in ("gpcc_dev_lift_encode_attr", "gpcc_dev_lift_decode_attr"):
         getattr(lib, name).argtypes = [vp, C.POINTER(LodParams), vp, i32, i64p, vp, vp, vp, vp, vp, i32]

@@ -51,6 +51,7 @@
 #include "pred_repair.hpp"
 #include "morton_sort.hpp"
 #include "residual_bins.hpp"
+#include "recolour_batch.hpp"
 #include "recolour_kernels.hpp"
 #include "slice_rdo.hpp"
 #include "spherical.hpp"
@@ -308,6 +309,8 @@ struct gpcc_ctx {
   hipEvent_t kd_event = nullptr;
   hipEvent_t inter_event = nullptr;  // inter-frame RAHT: the second candidate's stream joins the first
   int32_t* h_kd = nullptr;        // pinned: 2 x 4 counters
+  int32_t* h_rc_boxes = nullptr;  // pinned: the slices' bounding boxes of gpcc_dev_recolour_attrs, grown on demand
+  size_t h_rc_boxes_cap = 0;      // (ints)
   // what the entries did since the context was created (gpcc_ctx_stats)
   gpcc_ctx_stats_t stats{};
   // device buffers of the host tiers, kept between calls (pool_malloc)
@@ -2772,6 +2775,8 @@ gpcc_ctx_destroy(gpcc_ctx* ctx)
     hipHostFree(ctx->h_cx_stage);
   if (ctx->h_small)
     hipHostFree(ctx->h_small);
+  if (ctx->h_rc_boxes)
+    hipHostFree(ctx->h_rc_boxes);
   if (ctx->h_bounce)
     hipHostFree(ctx->h_bounce);
   for (int h = 0; h < 2; h++)
@@ -7235,4 +7240,81 @@ gpcc_recolour_attrs(
     ctx,
     recolour_impl(ctx, params, src_xyz, ns, tgt_xyz, nt, attrs, num_attrs, true, source_to_target_scale, target_to_source_offset),
     nt);
+}
+
+// ---- device tier: a batch of slices, the trees as forests (recolour_batch.hpp) ----------------
+namespace {
+
+// what rcb_run asks of its surroundings, from the context: pool blocks held through PoolScope (back in the pool on
+// every return path), the second tree stream of the host tier, pinned words
+struct RcBatchHost {
+  gpcc_ctx* ctx;
+  PoolScope pool;
+  std::unique_ptr<PoolScope> work;
+  explicit RcBatchHost(gpcc_ctx* c) : ctx(c), pool(c), work(new PoolScope(c)) {}
+  hipError_t take(size_t bytes, void** out, bool in_work) { return (in_work && work ? *work : pool).take_bytes(bytes, out); }
+  void end_work() { work.reset(); }
+  hipError_t upload(void* dst, const void* src, size_t bytes) { return h2d_user(ctx, dst, src, bytes, ctx->stream); }
+  hipError_t fork(hipStream_t* second)
+  {
+    hipError_t e = hipSuccess;
+    if (!ctx->kd_stream)
+      e = hipStreamCreateWithFlags(&ctx->kd_stream, hipStreamNonBlocking);
+    if (e == hipSuccess && !ctx->kd_event)
+      e = hipEventCreateWithFlags(&ctx->kd_event, hipEventDisableTiming);
+    if (e == hipSuccess)
+      e = hipEventRecord(ctx->kd_event, ctx->stream);
+    if (e == hipSuccess)
+      e = hipStreamWaitEvent(ctx->kd_stream, ctx->kd_event, 0);
+    *second = ctx->kd_stream;
+    return e;
+  }
+  hipError_t join()
+  {
+    hipError_t e = hipEventRecord(ctx->kd_event, ctx->kd_stream);
+    return e == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->kd_event, 0) : e;
+  }
+  int32_t* counters()
+  {
+    if (!ctx->h_kd && hipHostMalloc((void**)&ctx->h_kd, 8 * sizeof(int32_t)) != hipSuccess)
+      return nullptr;
+    return ctx->h_kd;
+  }
+  int32_t* boxes(size_t ints)
+  {
+    if (ctx->h_rc_boxes_cap < ints) {
+      if (ctx->h_rc_boxes)
+        hipHostFree(ctx->h_rc_boxes);
+      ctx->h_rc_boxes = nullptr;
+      ctx->h_rc_boxes_cap = 0;
+      const size_t cap = ints + ints / 2 + 96;
+      if (hipHostMalloc((void**)&ctx->h_rc_boxes, cap * sizeof(int32_t)) != hipSuccess)
+        return nullptr;
+      ctx->h_rc_boxes_cap = cap;
+    }
+    return ctx->h_rc_boxes;
+  }
+  int fail(int code, const char* msg) { return ::fail(code, std::string("gpcc_dev_recolour_attrs: ") + msg); }
+  Timer span(const char* name) { return Timer(ctx, name); }
+};
+
+}  // namespace
+
+extern "C" int
+gpcc_dev_recolour_attrs(
+  gpcc_ctx* ctx, const gpcc_recolour_params* params, int32_t num_slices, const int64_t* src_offsets,
+  const void* d_src_xyz, const int64_t* tgt_offsets, const void* d_tgt_xyz, const gpcc_dev_recolour_attr* attrs,
+  int32_t num_attrs, float source_to_target_scale, const int32_t* target_to_source_offsets)
+{
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  const RcBatchIn in = {num_slices, src_offsets, tgt_offsets, (const int32_t*)d_src_xyz, (const int32_t*)d_tgt_xyz,
+                        attrs,      num_attrs,   source_to_target_scale, target_to_source_offsets};
+  std::string why;
+  const int rc = rcb_check(params, in, &why);
+  if (rc != GPCC_OK)
+    return counted(ctx, fail(rc, "gpcc_dev_recolour_attrs: " + why), 0);
+  HIP_TRY(hipSetDevice(ctx->device));
+  RcBatchHost host(ctx);
+  return counted(ctx, rcb_run(host, *params, in, ctx->stream), tgt_offsets[num_slices]);
 }

@@ -68,6 +68,28 @@ kd_node_capacity(size_t n)
   return 2 * n + n / 4 + 64;
 }
 
+// A FOREST: the trees of R clouds (R >= 1, every one with at least one point, n points together) built by the
+// same level loop -- root r is node r, all roots are level 1.  The bounds, re-derived for R roots:
+//   level arrays  the level loop's nodes are nodes of R binary trees whose leaves hold at least one point each:
+//                 at most 2n - R of them, so the 2n + 2 entries of one tree hold a forest's as well;
+//   subtree list  every leaf of the level loop goes to the list.  The loop's internal nodes of ONE level are
+//                 disjoint ranges of more than kKdSub points, whatever tree they belong to: fewer than
+//                 n / kKdSub per level, fewer than 64 n / 1024 = n / 16 over kKdMaxDepth levels; a tree has one
+//                 leaf more than internal nodes, so the list holds fewer than n / 16 + R entries.  One tree's
+//                 n / 11 + 2 does NOT cover R roots (40 clouds of 8 points: 31 < 40): kd_sub_stride adds R;
+//   nodes         the level loop's ids are R + 2 per internal node < R + n / 8, the subtrees' blocks 2 per point:
+//                 one tree's capacity and R.
+inline size_t
+kd_forest_node_capacity(size_t n, size_t roots)
+{
+  return kd_node_capacity(n) + roots;
+}
+inline size_t
+kd_forest_sub_capacity(size_t n, size_t roots)
+{
+  return n / 11 + 2 + roots;
+}
+
 // the build's working set (the arrays of the level loop hold 2n + 2 nodes; node ids in order of creation)
 struct KdBuild {
   KdTree t;
@@ -86,8 +108,16 @@ struct KdBuild {
   long long* sums;   // [n / kKdScanBlock + 2]
   int32_t* counters; // [0] nodes created, [1] internal nodes of the level just split, [2] subtree roots,
                      // [3] the deepest level a subtree reached
-  int32_t* sub_list; // [2][n / 11 + 2] roots of the subtrees kd_subtree_kernel finishes, then their levels
+  int32_t* sub_list; // [2][kd_sub_stride] roots of the subtrees kd_subtree_kernel finishes, then their levels
+  int32_t roots;     // 0: one tree (KdLevelLoop::begin); R: a forest of R trees (begin_forest)
 };
+
+// entries of one half of sub_list: one tree's n / 11 + 2, and one per root of a forest
+__host__ __device__ __forceinline__ int
+kd_sub_stride(const KdBuild& b)
+{
+  return b.t.n / 11 + 2 + b.roots;
+}
 
 __device__ __forceinline__ int
 kd_lane()
@@ -238,6 +268,60 @@ kd_init_kernel(KdBuild b, const int32_t* __restrict__ bbox)
   }
 }
 
+// The forest's start: `off` = the R + 1 ascending offsets of the clouds in the concatenated position array (no
+// cloud empty).  vind holds indices into that array, pnode of a position is its cloud's root; the roots' boxes
+// follow from the first kd_minmax (kd_forest_boxes_kernel).
+__global__ __launch_bounds__(256) void
+kd_init_forest_kernel(KdBuild b, const int32_t* __restrict__ off, int roots)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < b.t.n) {
+    // the cloud of position i: the last r with off[r] <= i
+    int lo = 0, hi = roots;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (off[mid] <= i)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    b.t.vind[i] = i;
+    b.pnode[i] = lo;
+  }
+  if (i < roots) {
+    b.rng[2 * i] = off[i];
+    b.rng[2 * i + 1] = off[i + 1];
+    b.parent[i] = -1;
+    for (int a = 0; a < 3; a++) {
+      b.mm[6 * i + a] = 0x7fffffff;
+      b.mm[6 * i + 3 + a] = -0x7fffffff;
+    }
+  }
+  if (i == 0) {
+    b.counters[0] = roots;
+    b.counters[1] = 0;
+    b.counters[2] = 0;
+    b.counters[3] = 0;
+    b.flag[0] = 0;
+  }
+}
+
+// every root's tight bounds (kd_minmax over the batch: ONE launch whatever the number of clouds) become its box,
+// what the searches start from (root_box [R][6]: lo[3], hi[3]) and what the host looks at (bbox [R][6])
+__global__ __launch_bounds__(256) void
+kd_forest_boxes_kernel(KdBuild b, int roots, double* __restrict__ root_box, int32_t* __restrict__ bbox)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= roots)
+    return;
+  for (int a = 0; a < 6; a++) {
+    const int32_t v = b.mm[6 * r + a];
+    b.box[6 * r + a] = (double)v;
+    root_box[6 * r + a] = (double)v;
+    bbox[6 * r + a] = v;
+  }
+}
+
 // kd_minmax / kd_count: a wavefront takes a CONTIGUOUS chunk of kKdChunk positions and keeps what it has
 // gathered for the node it is in across its rounds -- the nodes of a level are contiguous ranges, so at
 // the upper levels a wavefront issues ONE set of atomics (with a round of positions per wavefront and
@@ -339,7 +423,7 @@ kd_split_kernel(KdBuild b, int nb, int ne, int level)
     b.t.nodes[k] = nd;
     const int slot = atomicAdd(&b.counters[2], 1);
     b.sub_list[slot] = k;
-    b.sub_list[b.t.n / 11 + 2 + slot] = level;
+    b.sub_list[kd_sub_stride(b) + slot] = level;
     return;
   }
   const double* bx = b.box + 6 * k;
@@ -652,7 +736,7 @@ kd_subtree_kernel(KdBuild b, int nsub)
     sm.st_node[0] = root;
     sm.st_l[0] = 0;
     sm.st_r[0] = cnt;
-    sm.st_lv[0] = b.sub_list[b.t.n / 11 + 2 + blockIdx.x];
+    sm.st_lv[0] = b.sub_list[kd_sub_stride(b) + blockIdx.x];
   }
   __builtin_amdgcn_wave_barrier();
   // the subtree's node ids: one block, two per point
@@ -829,6 +913,27 @@ struct KdLevelLoop {
     hipLaunchKernelGGL(kd_init_kernel, dim3((b.t.n + 255) / 256), dim3(256), 0, st, b, bbox);
     return hipGetLastError();
   }
+  // A forest of `roots` trees (kd_init_forest_kernel): the loop starts with the level [0, roots) and is the
+  // same from there -- its launches and its one wait per level do not depend on the number of trees.  bbox
+  // (device, [roots][6]) is ready behind what this enqueues.
+  hipError_t begin_forest(const KdBuild& build, const int32_t* off, int roots, double* root_box, int32_t* bbox,
+                          hipStream_t stream, int32_t* pinned4)
+  {
+    b = build;
+    b.roots = roots;
+    st = stream;
+    h = pinned4;
+    nb = 0;
+    ne = roots;
+    depth = 0;
+    phase = 0;
+    const int n = b.t.n;
+    const int sgrid = ((n + kKdChunk - 1) / kKdChunk + 3) / 4;
+    hipLaunchKernelGGL(kd_init_forest_kernel, dim3((n + 255) / 256), dim3(256), 0, st, b, off, roots);
+    hipLaunchKernelGGL(kd_minmax_kernel, dim3(sgrid), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(kd_forest_boxes_kernel, dim3((roots + 255) / 256), dim3(256), 0, st, b, roots, root_box, bbox);
+    return hipGetLastError();
+  }
   bool done() const { return phase == 2; }
 
   // enqueue the next piece of work and the copy of the counters behind it
@@ -960,9 +1065,11 @@ rc_worst(const RcKnn<K>& r, int k)
 // findNeighbors (:1200-1215) + searchLevel (:1308-1365).  The recursion's frames: the node, the
 // mindistsq it was entered with, and -- once its nearer child has returned -- the entry of
 // dists[] that the second descent replaced.  phase 0 = entered, 1 = nearer child done, 2 = both.
+// `root`, `root_lo`, `root_hi`: the tree of a forest the walk starts in, with that tree's root box.
 template<int K>
 __device__ __forceinline__ void
-rc_kd_search(const KdTree& t, const double q[3], int k, RcKnn<K>& r)
+rc_kd_search_from(const KdTree& t, int root, const double root_lo[3], const double root_hi[3], const double q[3], int k,
+                  RcKnn<K>& r)
 {
 #pragma clang fp contract(off)
   r.count = 0;
@@ -975,19 +1082,19 @@ rc_kd_search(const KdTree& t, const double q[3], int k, RcKnn<K>& r)
   double distsq = 0.0;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    if (q[a] < t.root_lo[a]) {
-      dists[a] = (q[a] - t.root_lo[a]) * (q[a] - t.root_lo[a]);
+    if (q[a] < root_lo[a]) {
+      dists[a] = (q[a] - root_lo[a]) * (q[a] - root_lo[a]);
       distsq += dists[a];
     }
-    if (q[a] > t.root_hi[a]) {
-      dists[a] = (q[a] - t.root_hi[a]) * (q[a] - t.root_hi[a]);
+    if (q[a] > root_hi[a]) {
+      dists[a] = (q[a] - root_hi[a]) * (q[a] - root_hi[a]);
       distsq += dists[a];
     }
   }
   int32_t st_node[kKdMaxDepth + 1];  // node << 2 | phase
   double st_mind[kKdMaxDepth + 1], st_dst[kKdMaxDepth + 1];
   int sp = 0;
-  st_node[0] = 0;
+  st_node[0] = root << 2;
   st_mind[0] = distsq;
   st_dst[0] = 0.0;
   while (sp >= 0) {
@@ -1043,6 +1150,14 @@ rc_kd_search(const KdTree& t, const double q[3], int k, RcKnn<K>& r)
       sp--;
     }
   }
+}
+
+// one tree: root 0 with the tree's own box
+template<int K>
+__device__ __forceinline__ void
+rc_kd_search(const KdTree& t, const double q[3], int k, RcKnn<K>& r)
+{
+  rc_kd_search_from<K>(t, 0, t.root_lo, t.root_hi, q, k, r);
 }
 
 }  // namespace gpcc

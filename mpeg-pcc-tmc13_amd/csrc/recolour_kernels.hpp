@@ -19,6 +19,7 @@
 //   rc_backward      per source point: its nearest target points -> (target, dist)
 //   rc_list_fill     the backward lists, one contiguous range per target
 //   rc_blend         per target point: list in the reference's order, centroid, refinement
+//   rcb_*            the same stages over a batch of slices resident on the device (recolour_batch.hpp)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -94,6 +95,26 @@ rc_limit(double v)
   return v < 512 ? v : 1.7976931348623157e308;
 }
 
+// the two searches' query points: target t in the source's frame (pointset_processing.cpp:299-300 / 662-663) and
+// source point s in the target's (:399-400 / 753-754); `off` = target_to_source_offset (a slice's own row in a batch)
+__device__ __forceinline__ void
+rc_forward_query(const int32_t* __restrict__ tgt_xyz, int t, const int32_t off[3], double t2s, double q[3])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    q[a] = (double)(tgt_xyz[3 * t + a] + off[a]) * t2s;
+}
+
+__device__ __forceinline__ void
+rc_backward_query(const int32_t* __restrict__ src_xyz, int s, const int32_t off[3], double s2t, double q[3])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    q[a] = (double)src_xyz[3 * s + a] * s2t - (double)off[a];
+}
+
 // wavefronts per SIMD the two search kernels are compiled for (0: the compiler's choice); an experiment knob
 #ifndef GPCC_RC_WAVES
 #define GPCC_RC_WAVES 0
@@ -120,9 +141,7 @@ rc_forward_kernel(RcCtx cx)
   const double max_a = rc_limit(p.max_attribute_dist2_fwd);
   const double clip_max = (double)((1 << p.bitdepth) - 1);
   double q[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    q[a] = (double)(cx.tgt.xyz[3 * t + a] + cx.off[a]) * cx.t2s;
+  rc_forward_query(cx.tgt.xyz, t, cx.off, cx.t2s, q);
   RcKnn<K> r;
   rc_kd_search<K>(cx.src, q, kf, r);
   if (cx.nearest) {
@@ -360,9 +379,7 @@ rc_forward_attrs_kernel(RcCtx cx, RcAttrs at)
   const int kf = p.num_neighbours_fwd;
   const double max_a = rc_limit(p.max_attribute_dist2_fwd);
   double q[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    q[a] = (double)(cx.tgt.xyz[3 * t + a] + cx.off[a]) * cx.t2s;
+  rc_forward_query(cx.tgt.xyz, t, cx.off, cx.t2s, q);
   RcKnn<K> r;
   rc_kd_search<K>(cx.src, q, kf, r);
   if (cx.nearest) {
@@ -418,9 +435,7 @@ rc_backward_kernel(RcCtx cx)
   const int kb = cx.p.num_neighbours_bwd;
   const double max_g = rc_limit(cx.p.max_geometry_dist2_bwd);
   double q[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    q[a] = (double)cx.src.xyz[3 * s + a] * cx.s2t - (double)cx.off[a];
+  rc_backward_query(cx.src.xyz, s, cx.off, cx.s2t, q);
   RcKnn<K> r;
   rc_kd_search<K>(cx.tgt, q, kb, r);
 #pragma unroll

@@ -306,6 +306,11 @@ class RecolourAttr(C.Structure):
     _fields_ = [("src", C.c_void_p), ("tgt", C.c_void_p), ("c", C.c_int32), ("bitdepth", C.c_int32)]
 
 
+class DevRecolourAttr(C.Structure):
+    """ctypes mirror of gpcc_dev_recolour_attr: one attribute of a gpcc_dev_recolour_attrs call (device addresses)."""
+    _fields_ = [("d_src", C.c_void_p), ("d_tgt", C.c_void_p), ("c", C.c_int32), ("bitdepth", C.c_int32)]
+
+
 def recolour_params(bitdepth=8, search_range=1, k_fwd=8, k_bwd=1, weighted_fwd=True, weighted_bwd=True,
                     skip_fwd=True, skip_bwd=False, dist_offset_fwd=4.0, dist_offset_bwd=4.0,
                     max_geom_fwd=1000.0, max_geom_bwd=1000.0, max_attr_fwd=1000.0, max_attr_bwd=1000.0):

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .params import RahtParams, RecolourAttr
+from .params import DevRecolourAttr, RahtParams, RecolourAttr
 
 
 class Context:
@@ -503,6 +503,24 @@ class Context:
                 e.buffers = outs
                 raise
         return outs
+
+    def dev_recolour_attrs(self, params, src_offsets, d_src_xyz, tgt_offsets, d_tgt_xyz, attrs, scale=1.0, offsets=None):
+        """gpcc_dev_recolour_attrs: every attribute of a batch of slices, everything on the device; the slices' k-d
+        trees are built as two forests.  src_offsets / tgt_offsets: [S + 1] (gpcc_src_partition's layout); attrs: a
+        list of (d_src, d_tgt, c, bitdepth) with device addresses; offsets: [S, 3] target_to_source_offset per slice
+        (None: zeros).  Enqueued on the context's stream: d_tgt is valid after synchronize()."""
+        S = len(src_offsets) - 1
+        so = (C.c_int64 * (S + 1))(*[int(o) for o in src_offsets])
+        to = (C.c_int64 * (S + 1))(*[int(o) for o in tgt_offsets])
+        table = (DevRecolourAttr * max(len(attrs), 1))()
+        for i, (d_src, d_tgt, c, bitdepth) in enumerate(attrs):
+            table[i].d_src, table[i].d_tgt, table[i].c, table[i].bitdepth = d_src, d_tgt, int(c), int(bitdepth)
+        flat = np.zeros(3 * max(S, 0), dtype=np.int32) if offsets is None else \
+            np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        off = (C.c_int32 * max(len(flat), 1))(*[int(v) for v in flat])
+        _lib.check(self._lib.gpcc_dev_recolour_attrs(
+            self._h, C.byref(params), S, so, C.c_void_p(d_src_xyz), to, C.c_void_p(d_tgt_xyz), table, len(attrs),
+            C.c_float(scale), off))
 
     # ---- unique-position quantisation and source partitions ---------------
     def quantize_positions(self, params, src_xyz, fill=None):

@@ -1016,6 +1016,49 @@ int gpcc_dev_zero_run_unpack(
   gpcc_ctx* ctx, int32_t num_slices, const int64_t* offsets, const int64_t* sym_offsets,
   const int32_t* runs, const int32_t* values, void* d_coeffs, int32_t c, int32_t planar);
 
+/* The RAHT slice coder of the device tier: encode/decode{Colors,Reflectances}TransformRaht
+ * (AttributeEncoder.cpp:1214-1302, 1306-1375; AttributeDecoder.cpp:527-609, 613-674) for a BATCH of slices resident
+ * in HBM, from point order, in one call: the Morton sort, the gather of the attributes into Morton order, the
+ * per-point region QP offsets (QpSet::regionQpOffset), the transform, the clip of the reconstruction to the bit depth
+ * and the scatter back by original index.  For slice s (n_s points, base b = offsets[s]):
+ *   d_xyz    + 3*b  int32 [n_s][3]  point order, coordinates in [0, 2^21) (not inspected on the host;
+ *                                   gpcc_ctx_set_morton_bits is the hint, as for gpcc_dev_attr_morton_sort)
+ *   d_attrs  + c*b  int32 [n_s][c]  point order.  Encoder in: the source attributes.  Encoder and decoder out: the
+ *                                   reconstruction clipped to [0, 2^bitdepth - 1] -- what gpcc_dev_attr_ref_crop
+ *                                   takes as the previous frame
+ *   d_coeffs + c*b  int32 [c][n_s]  planar, Morton order: what gpcc_dev_raht_forward leaves and
+ *                                   gpcc_dev_residual_bins (planar = 1) / gpcc_dev_zero_run_unpack use
+ *   d_order  + b    int32 [n_s]     out, may be NULL: the slice-local original index of the i-th sorted point
+ *   regions  host [num_slices], may be NULL: regions[s] are slice s's own boxes; the offset of the first box that
+ *            contains a point is added, bounds inclusive.  If no slice names a region (or regions is NULL) the
+ *            transform runs without an offset array, exactly as gpcc_dev_raht_forward with d_qp_off == NULL;
+ *            otherwise the slices without regions get zeros.  The table is uploaded with the call
+ *            (sizeof(gpcc_qp_regions) bytes per slice, in device memory, never a kernel argument).
+ * One parameter block serves the batch, as for gpcc_dev_raht_forward.  Per slice the result equals that slice's own
+ * gpcc_raht_encode_attr / gpcc_raht_encode_attr_packed_regions / gpcc_raht_decode_attr_regions, whatever stands
+ * next to it in the batch.  Neither the launches nor the host waits depend on num_slices, and the call adds no wait
+ * to those of gpcc_dev_attr_morton_sort and gpcc_dev_raht_forward; it enqueues and returns, results are valid after
+ * gpcc_ctx_synchronize.  A device-side error is the sticky word of the transform.
+ * Workspace: what has to outlive the sort and the transform (codes, order, sorted attributes, region offsets, the
+ * tables) comes from the context's pool; gpcc_ctx_reserve is NOT extended to it (the first call of a shape
+ * allocates, a repeated call allocates nothing).
+ * GPCC_ERR_INVALID_ARG, decided on the host ahead of any launch, no byte of the caller's buffers written and the
+ * pool whole: a null ctx, params, offsets, d_xyz, d_attrs or d_coeffs; num_slices < 1, offsets[0] != 0, an empty or
+ * unordered slice, more than 2^29 points; c outside 1..3 or a parameter block gpcc_dev_raht_forward refuses;
+ * bitdepth outside [1, 16]; a num_qp_regions outside [0, GPCC_MAX_QP_REGIONS] in any slice.  All but the null ctx
+ * are checked ahead of the context.
+ * Not part of these entries: the multi tier, the shim (seam 3 stays on the host-tier entries), bench.py, inter
+ * RAHT, per-slice parameter blocks (QP layers per slice), and the host-tier slice driver, which is not re-expressed
+ * through these kernels. */
+int gpcc_dev_raht_encode_attr(
+  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, int32_t num_slices,
+  const int64_t* offsets, const void* d_xyz, void* d_attrs, void* d_coeffs, void* d_order, int32_t c,
+  int32_t bitdepth);
+int gpcc_dev_raht_decode_attr(
+  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, int32_t num_slices,
+  const int64_t* offsets, const void* d_xyz, void* d_attrs, const void* d_coeffs, void* d_order, int32_t c,
+  int32_t bitdepth);
+
 /* ------------------------------------------------------------------ */
 /* device tier of the LoD build and the lifting coder                   */
 /* The same operations on buffers resident in HBM, num_slices slices back to

@@ -58,6 +58,7 @@
 #include "quantize_positions.hpp"
 #include "ref_crop.hpp"
 #include "symbol_stream.hpp"
+#include "raht_marshal.hpp"
 
 using namespace gpcc;
 
@@ -5904,6 +5905,130 @@ gpcc_dev_zero_run_unpack(
 {
   return counted(
     ctx, dev_zero_run_unpack(ctx, num_slices, offsets, sym_offsets, runs, values, d_coeffs, c, planar),
+    batch_points(offsets, num_slices));
+}
+
+}  // extern "C"
+
+// ---- device tier of the RAHT slice coder (raht_marshal.hpp) ---------------------------
+namespace {
+
+// encode/decode{Colors,Reflectances}TransformRaht for a batch in HBM, from point order: Morton sort, gather (with
+// the region offsets), transform, clip and scatter.  Enqueues and returns like dev_transform.  The sort and the
+// transform both lay the arena out anew, so what has to outlive them -- codes, order, sorted attributes, region
+// offsets, the slice and region tables -- are blocks of the pool.
+int
+dev_raht_attr(
+  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, bool encoder, int32_t num_slices,
+  const int64_t* offsets, const void* d_xyz, void* d_attrs, void* d_coeffs, void* d_order, int32_t c, int32_t bitdepth)
+{
+  if (!d_xyz || !d_attrs || !d_coeffs)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  int r = check_batch_offsets(num_slices, offsets);
+  if (r)
+    return r;
+  r = check_params(params, c, encoder);
+  if (r)
+    return r;
+  if (bitdepth < 1 || bitdepth > 16)
+    return fail(GPCC_ERR_INVALID_ARG, "bitdepth outside [1, 16]");
+  bool any_region = false;
+  for (int s = 0; regions && s < num_slices; s++) {
+    if (regions[s].num_qp_regions < 0 || regions[s].num_qp_regions > GPCC_MAX_QP_REGIONS)
+      return fail(GPCC_ERR_INVALID_ARG, "num_qp_regions out of range");
+    any_region = any_region || regions[s].num_qp_regions > 0;
+  }
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  const size_t S = (size_t)num_slices, N = (size_t)offsets[num_slices];
+  const size_t table_bytes = (S + 1) * sizeof(int32_t);
+  const size_t region_at = (table_bytes + 15) & ~size_t(15);
+  const size_t meta_bytes = region_at + (any_region ? S * sizeof(gpcc_qp_regions) : 0);
+
+  // the largest first: the pool's best fit then finds every block of the previous call of this shape again
+  PoolScope pool(ctx);
+  int64_t* d_m = nullptr;
+  int32_t *d_o = (int32_t*)d_order, *d_a = nullptr, *d_q = nullptr;
+  char* d_meta = nullptr;
+  struct Want {
+    size_t bytes;
+    void** out;
+  } want[5] = {
+    {sizeof(int64_t) * N, (void**)&d_m},
+    {sizeof(int32_t) * N * c, (void**)&d_a},
+    {any_region ? sizeof(int32_t) * 2 * N : 0, (void**)&d_q},
+    {d_order ? 0 : sizeof(int32_t) * N, (void**)&d_o},
+    {meta_bytes, (void**)&d_meta},
+  };
+  std::stable_sort(want, want + 5, [](const Want& x, const Want& y) { return x.bytes > y.bytes; });
+  for (const Want& w : want)
+    if (w.bytes)
+      HIP_TRY(pool.take_bytes(w.bytes, w.out));
+
+  std::vector<char> meta(meta_bytes, 0);
+  for (size_t s = 0; s <= S; s++)
+    ((int32_t*)meta.data())[s] = (int32_t)offsets[s];
+  if (any_region)
+    memcpy(meta.data() + region_at, regions, S * sizeof(gpcc_qp_regions));
+  HIP_TRY(h2d_user(ctx, d_meta, meta.data(), meta_bytes, st));
+
+  r = dev_morton_sort(ctx, num_slices, offsets, d_xyz, d_m, d_o);
+  if (r)
+    return r;
+
+  MarshalArgs a{};
+  a.pt_off = (const int32_t*)d_meta;
+  a.regions = any_region ? (const gpcc_qp_regions*)(d_meta + region_at) : nullptr;
+  a.order = d_o;
+  a.xyz = (const int32_t*)d_xyz;
+  a.point = (int32_t*)d_attrs;
+  a.sorted = d_a;
+  a.qp_off = d_q;
+  a.n = (int32_t)N;
+  a.c = c;
+  a.num_slices = num_slices;
+  a.clip_max = (1 << bitdepth) - 1;
+  a.attrs = encoder ? 1 : 0;
+  auto span = [&](const char* name) { return Timer(ctx, name); };
+  HIP_TRY(raht_gather_launch(st, a, span));
+  if (encoder)
+    HIP_TRY(hipMemsetAsync(d_coeffs, 0, sizeof(int32_t) * N * c, st));
+
+  // (without a region in the batch: no offset array, so that the compact level pass stays eligible)
+  r = dev_transform(ctx, params, encoder, num_slices, offsets, d_m, d_q, d_a, d_coeffs, c, ctx->morton_bits);
+  if (r)
+    return r;
+  HIP_TRY(raht_clip_scatter_launch(st, a, span));
+  return GPCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int
+gpcc_dev_raht_encode_attr(
+  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, int32_t num_slices,
+  const int64_t* offsets, const void* d_xyz, void* d_attrs, void* d_coeffs, void* d_order, int32_t c, int32_t bitdepth)
+{
+  return counted(
+    ctx, dev_raht_attr(ctx, params, regions, true, num_slices, offsets, d_xyz, d_attrs, d_coeffs, d_order, c, bitdepth),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_raht_decode_attr(
+  gpcc_ctx* ctx, const gpcc_raht_params* params, const gpcc_qp_regions* regions, int32_t num_slices,
+  const int64_t* offsets, const void* d_xyz, void* d_attrs, const void* d_coeffs, void* d_order, int32_t c,
+  int32_t bitdepth)
+{
+  return counted(
+    ctx,
+    dev_raht_attr(
+      ctx, params, regions, false, num_slices, offsets, d_xyz, d_attrs, const_cast<void*>(d_coeffs), d_order, c, bitdepth),
     batch_points(offsets, num_slices));
 }
 

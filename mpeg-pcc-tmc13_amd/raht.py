@@ -178,6 +178,23 @@ class Context:
         _lib.check(self._lib.gpcc_dev_attr_morton_sort(
             self._h, len(offsets) - 1, off, C.c_void_p(d_xyz), C.c_void_p(d_morton), C.c_void_p(d_order)))
 
+    def dev_raht_attr(self, encode, params, offsets, d_xyz, d_attrs, d_coeffs, c, bitdepth=8, regions=None, d_order=None):
+        """gpcc_dev_raht_encode_attr / _decode_attr: the RAHT slice coder for a batch in HBM, from point order.
+        d_attrs [n, c] point order (encode: in, the source; out: the clipped reconstruction), d_coeffs [c, n_s]
+        planar per slice in Morton order, d_order [n] out or None; regions: None or one QpRegions per slice
+        (params.qp_regions(...)).  Enqueued on the context's stream."""
+        from .params import QpRegions
+        ns = len(offsets) - 1
+        off = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        reg = None
+        if regions is not None:
+            assert len(regions) == ns, "one QpRegions per slice"
+            reg = (QpRegions * ns)(*regions)
+        fn = self._lib.gpcc_dev_raht_encode_attr if encode else self._lib.gpcc_dev_raht_decode_attr
+        _lib.check(fn(self._h, C.byref(params), C.cast(reg, C.c_void_p) if reg is not None else None, ns, off,
+                      C.c_void_p(d_xyz), C.c_void_p(d_attrs), C.c_void_p(d_coeffs), C.c_void_p(d_order or 0), int(c),
+                      int(bitdepth)))
+
     # ---- attribute positions in the pseudo-spherical domain --------------
     def attr_to_spherical(self, params, xyz, out=None):
         """gpcc_attr_to_spherical -> (positions int32 [n, 3], bounding box int32 [2, 3] of the unscaled

@@ -353,8 +353,13 @@ pred_icp_resolve_kernel(PredCtx cx)
 // the reference's result.  Each pass is exact up to its first wrong decision, and a wrong
 // state decays by 1/64 per predictor, so a handful of passes settle a slice.
 // The estimate takes log2 of integers below 2^20: the table is filled by the host's libm
-// (the reference's own log2), the sums are evaluated in the reference's order without
-// contraction -- identical doubles, identical decisions.
+// (the reference's own log2), and every term is added in the reference's order without
+// contraction: bitsPtColor (:163-199) carries ONE running sum through the three components,
+// so pred_rate_component takes that sum and returns it.  (Double addition is not
+// associative: with a sum per component, added afterwards, two direct predictors of equal
+// distortion and nearly equal rate -- modes that only swap a parity bit between the second
+// and the third component -- were ranked the other way round from 12 bits upwards.)
+// Identical doubles, identical decisions.
 constexpr int kRateScale = 1 << 20, kRateWindowLog2 = 6;
 
 __device__ __forceinline__ double
@@ -364,11 +369,10 @@ pred_log2i(const PredCtx& cx, int64_t v)
 }
 
 __device__ __forceinline__ double
-pred_rate_component(const PredCtx& cx, const int32_t* rm, int k, int32_t value)
+pred_rate_component(const PredCtx& cx, const int32_t* rm, int k, int32_t value, double bits)
 {
 #pragma clang fp contract(off)
   const int l2 = 20;  // ilog2(scaleRes)
-  double bits = 0;
   bits += value ? l2 - pred_log2i(cx, rm[k]) : l2 - pred_log2i(cx, kRateScale - rm[k]);
   const int mag = value < 0 ? -value : value;
   if (mag) {
@@ -397,7 +401,7 @@ pred_rate_refl(const PredCtx& cx, const int32_t* rm, int avail, int32_t value, i
     value = (a << 1) + (mode & 1);
   }
   double bits = 0;
-  bits += pred_rate_component(cx, rm, 0, value);
+  bits = pred_rate_component(cx, rm, 0, value, bits);
   return bits;
 }
 
@@ -420,7 +424,7 @@ pred_rate_colour(const PredCtx& cx, const int32_t* rm, int avail, const int64_t 
   }
   double bits = 0;
   for (int k = 0; k < 3; k++)
-    bits += pred_rate_component(cx, rm, k, v[k]);
+    bits = pred_rate_component(cx, rm, k, v[k], bits);
   return bits;
 }
 

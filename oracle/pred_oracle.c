@@ -80,11 +80,14 @@ rate_update(rate_model_t* m, const int32_t* v, int c)
   }
 }
 
+/* one component's terms of bitsPtColor / bitsPtRefl, added to the running sum `bits` one by
+ * one: the reference carries ONE accumulator through all three components, and double
+ * addition is not associative -- per-component sums added afterwards choose another mode
+ * where two direct predictors tie in distortion and nearly tie in rate */
 static double
-rate_bits_component(const rate_model_t* m, int k, int32_t value)
+rate_bits_component(const rate_model_t* m, int k, int32_t value, double bits)
 {
   const int l2 = 20; /* ilog2(scaleRes) */
-  double bits = 0;
   bits += value ? l2 - log2(m->gt0[k]) : l2 - log2(kScaleRes - m->gt0[k]);
   const int mag = abs(value);
   if (mag) {
@@ -110,7 +113,7 @@ rate_bits_refl(const rate_model_t* m, int32_t value, int mode)
     value = (abs(value) << 1) + (mode & 1);
   }
   double bits = 0;
-  bits += rate_bits_component(m, 0, value);
+  bits = rate_bits_component(m, 0, value, bits);
   return bits;
 }
 
@@ -131,7 +134,7 @@ rate_bits_colour(const rate_model_t* m, const int64_t r[3], int mode)
   }
   double bits = 0;
   for (int k = 0; k < 3; k++)
-    bits += rate_bits_component(m, k, v[k]);
+    bits = rate_bits_component(m, k, v[k], bits);
   return bits;
 }
 

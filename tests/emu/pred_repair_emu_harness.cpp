@@ -3,9 +3,9 @@
 // walk of pred_walk_kernel over what they left undecided -- under the CPU wavefront emulator.
 // The kernels are the library's (pred_kernels.hpp); the host-side decisions (when the walk takes
 // over, whether it is complete) are the library's too (pred_repair.hpp).  One or three
-// components, neighbours in a reference frame or not, any number of LoDs, one QP layer.  The
-// persistent kernels run as ONE workgroup; the inclusive scan the library runs on the device
-// (rc_scan) is a host loop here.
+// components, neighbours in a reference frame or not, any number of LoDs, one QP layer,
+// per-point QP offsets.  The persistent kernels run as ONE workgroup; the inclusive scan the
+// library runs on the device (rc_scan) is a host loop here.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -47,7 +47,7 @@ int
 run(
   const gpcc_pred_params* p, int32_t n, const int32_t* nc, const int32_t* ni, const int32_t* nw, const int32_t* inter_ref,
   const int32_t* indexes, int32_t* attrs, const int32_t* attrs_ref, int32_t n_ref, int32_t repair_after, int32_t* values,
-  int8_t* icp, int64_t* stats)
+  int8_t* icp, int64_t* stats, const int32_t* qp_off)
 {
   std::vector<void*> blocks;
   const size_t N = (size_t)n, NE = N + (size_t)n_ref;
@@ -77,7 +77,7 @@ run(
   cx.ni = d_ni;
   cx.nw = nw;
   cx.indexes = indexes;
-  cx.qp_off = nullptr;
+  cx.qp_off = qp_off;
   cx.attrs = attrs;
   cx.values = values;
   cx.icp = carve<int8_t>(&blocks, GPCC_MAX_LODS * 3);
@@ -211,18 +211,21 @@ run(
 // attrs [n][c] in: source, out: reconstruction (point order); values [n][c] out (coding order); icp [32][3] out;
 // inter_ref / attrs_ref: null / n_ref = 0 without a reference frame; repair_after <= 0: the library's default;
 // stats [7] out: passes, differences the walk started from, predictors walked, stretches, longest stretch, the first
-// and the last difference (-1: the walk was not needed)
+// and the last difference (-1: the walk was not needed); qp_off [n][2] in point order: the per-point QP offsets of
+// the slice's regions, or null
 extern "C" int
 pred_repair_emu_encode(
   const gpcc_pred_params* p, int32_t n, int32_t c, const int32_t* nc, const int32_t* ni, const int32_t* nw,
   const int32_t* inter_ref, const int32_t* indexes, int32_t* attrs, const int32_t* attrs_ref, int32_t n_ref,
-  int32_t repair_after, int32_t* values, int8_t* icp, int64_t* stats)
+  int32_t repair_after, int32_t* values, int8_t* icp, int64_t* stats, const int32_t* qp_off)
 {
   if (n <= 0 || (c != 1 && c != 3) || p->max_num_direct_predictors < 1 || p->scalable_lifting_enabled_flag
       || (n_ref > 0 && c != 1))
     return -1;
-  return c == 1 ? run<1>(p, n, nc, ni, nw, inter_ref, indexes, attrs, attrs_ref, n_ref, repair_after, values, icp, stats)
-                : run<3>(p, n, nc, ni, nw, inter_ref, indexes, attrs, attrs_ref, n_ref, repair_after, values, icp, stats);
+  return c == 1 ? run<1>(p, n, nc, ni, nw, inter_ref, indexes, attrs, attrs_ref, n_ref, repair_after, values, icp, stats,
+                         qp_off)
+                : run<3>(p, n, nc, ni, nw, inter_ref, indexes, attrs, attrs_ref, n_ref, repair_after, values, icp, stats,
+                         qp_off);
 }
 
 // the switch as the library reads it from its environment text

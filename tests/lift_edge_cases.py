@@ -279,7 +279,9 @@ class FixtureWriter:
             for k in range(a.shape[1]):
                 self._column(f"{name}/{k}", a[:, k], None if base is None else f"{base}/{k}")
 
-    def save(self, path):
+    def save(self, path, date_time=None):
+        """date_time: the time stamp of every member (a zip member carries the time of writing otherwise, and two
+        runs differ in those bytes)"""
         out = {f"blob{i}": np.concatenate(b).astype(_DTYPES[i]) if b else np.zeros(0, _DTYPES[i])
                for i, b in enumerate(self.blobs)}
         out["table"] = np.array(self.rows, np.int64).reshape(-1, 4)
@@ -293,7 +295,8 @@ class FixtureWriter:
             for k, v in out.items():
                 b = io.BytesIO()
                 np.lib.format.write_array(b, np.asanyarray(v), allow_pickle=False)
-                z.writestr(k + ".npy", b.getvalue())
+                member = k + ".npy" if date_time is None else zipfile.ZipInfo(k + ".npy", date_time)
+                z.writestr(member, b.getvalue(), compress_type=zipfile.ZIP_LZMA)
 
 
 class Fixture:

@@ -1098,6 +1098,57 @@ int gpcc_dev_lift_decode_attr(
   int32_t num_slices, const int64_t* offsets, const void* d_xyz, void* d_attrs,
   const void* d_coeffs, const int8_t* lcp_coeffs, void* d_indexes, int32_t c);
 
+/* gpcc_dev_lift_forward / _inverse: gpcc_lift_forward / gpcc_lift_inverse for a BATCH of slices over LoD structures
+ * the caller already holds in HBM, exactly as gpcc_dev_lod_build wrote them -- so a slice with several attributes
+ * on one geometry (colour and reflectance) pays the LoD build once: gpcc_dev_lod_build, then one of these calls per
+ * attribute (the reference's cached _lods, AttributeLods::isReusable).  For slice s (n_s points, base
+ * b = offsets[s]):
+ *   d_neigh_count  + b     int32 [n_s]     predictor order, neighbour indices slice relative
+ *   d_neigh_index  + 3*b   int32 [n_s][3]
+ *   d_neigh_weight + 3*b   int32 [n_s][3]  after computeWeights
+ *   d_indexes      + b     int32 [n_s]     point index of each predictor
+ *   d_attrs        + c*b   int32 [n_s][c]  point order.  Forward in: the source.  Forward and inverse out: the
+ *                                          reconstruction, rounded and clipped to [0, 2^bitdepth - 1]
+ *   d_coeffs       + c*b   int32 [n_s][c]  coding order: the layout of gpcc_dev_lift_encode_attr, which
+ *                                          gpcc_dev_residual_bins (planar = 0) reads
+ *   d_xyz          + 3*b   int32 [n_s][3]  point order; may be NULL when no slice names a QP region
+ *   lift   host [num_slices], input only: num_lods / num_points_in_lod as gpcc_dev_lod_build returned them for the
+ *          slice; QP layers, bitdepth, the LCP flag, scalable_lifting_enabled_flag (the quantisation weights of a
+ *          whole-slice scalable structure) and the qp_region_* fields are PER SLICE.  Where a slice names regions
+ *          the offset of a point is formed on the spot from d_xyz[b + indexes[i]] and the slice's boxes (the first
+ *          box that contains the point, bounds inclusive); no [N][2] array is built, slices without regions get zeros.
+ *   lcp_coeffs host [num_slices][GPCC_MAX_LODS] (c == 3 and the flag set): forward out, written for the slices
+ *          with the flag; inverse in.  May be NULL when no slice needs it.
+ * Per slice the results are those of its own gpcc_lift_forward / gpcc_lift_inverse, whatever stands next to it in
+ * the batch.  c is 1..3.
+ * Launches: a step is one LoD transition of EVERY slice at once (csrc/lift_batch.hpp), so with L the largest
+ * num_lods of the batch a forward call is at most 7 + 7 (L - 1) kernel launches and an inverse call at most
+ * 5 + 4 (L - 1), whatever num_slices is; the per-slice tables are uploaded once.  The call returns when the batch is
+ * done, with exactly one host wait, at its end; the forward call's lcp_coeffs come back with that wait.
+ * The structure is not inspected on the host.  A check kernel runs first and states what gpcc_lift_forward checks
+ * on the host: counts in 0..3, d_indexes in [0, n_s), every neighbour index in [0, num_points_in_lod[l - 1]) of its
+ * predictor's level l.  When it fails no later kernel of the call dereferences anything, the call returns
+ * GPCC_ERR_INVALID_ARG and no byte of d_attrs, d_coeffs or lcp_coeffs has been written.
+ * Workspace: the working arrays (16 + 16 c bytes per point of the batch), the LCP sums and the tables are blocks of
+ * the context's pool; gpcc_ctx_reserve is NOT extended to it (the first call of a shape allocates, a repeated call
+ * allocates nothing).
+ * GPCC_ERR_INVALID_ARG, decided on the host ahead of any launch, no byte written and the pool whole: a null ctx,
+ * lift, offsets, structure array, d_attrs or d_coeffs; num_slices < 1 (or above 2^18), offsets[0] != 0, an empty or
+ * unordered slice, more than 2^29 points; c outside 1..3; a lift[s] that gpcc_lift_forward refuses for n_s, or whose
+ * num_points_in_lod[0] is negative; a bitdepth outside [1, 16]; a num_qp_regions outside [0, GPCC_MAX_QP_REGIONS];
+ * a region in any slice with d_xyz == NULL; the LCP flag with c == 3 and lcp_coeffs == NULL.  All but the null ctx
+ * are checked ahead of the context.
+ * Not part of these entries: partial decode, inter prediction, the predicting transform, the multi tier, the shim,
+ * bench.py.  gpcc_dev_lift_encode_attr is not re-expressed through these kernels. */
+int gpcc_dev_lift_forward(
+  gpcc_ctx* ctx, const gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets, const void* d_neigh_count,
+  const void* d_neigh_index, const void* d_neigh_weight, const void* d_indexes, const void* d_xyz, void* d_attrs,
+  void* d_coeffs, int8_t* lcp_coeffs, int32_t c);
+int gpcc_dev_lift_inverse(
+  gpcc_ctx* ctx, const gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets, const void* d_neigh_count,
+  const void* d_neigh_index, const void* d_neigh_weight, const void* d_indexes, const void* d_xyz, void* d_attrs,
+  const void* d_coeffs, const int8_t* lcp_coeffs, int32_t c);
+
 /* gpcc_dev_lift_decode_attr_partial: gpcc_lift_decode_attr_partial for every slice of a
  * batch resident in HBM.  One min_geom_node_size_log2 for the call (a decoder stops every
  * slice at the same node size); geom_num_points is a HOST array [num_slices], the full

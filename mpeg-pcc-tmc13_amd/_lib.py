@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "gpcc_ctx_reserve",
     "gpcc_dev_residual_bins", "gpcc_dev_zero_run_unpack",
     "gpcc_dev_raht_encode_attr", "gpcc_dev_raht_decode_attr",
+    "gpcc_dev_lift_forward", "gpcc_dev_lift_inverse",
     "gpcc_quantize_positions", "gpcc_src_partition",
     "gpcc_debug_alloc_events", "gpcc_debug_pool_in_use", "gpcc_debug_has_experiments", "gpcc_debug_guard_checks", "gpcc_debug_rate_sum",
     "gpcc_debug_rdoq_threshold", "gpcc_debug_rdoq_resolve",
@@ -192,6 +193,9 @@ def load():
     # the RAHT slice coder of the device tier: a batch from point order in one call
     for name in ("gpcc_dev_raht_encode_attr", "gpcc_dev_raht_decode_attr"):
         getattr(lib, name).argtypes = [vp, pp, vp, i32, i64p, vp, vp, vp, vp, i32, i32]
+    # the lifting transform of a batch over LoD structures held in HBM (lift: LiftParams [num_slices], host)
+    for name in ("gpcc_dev_lift_forward", "gpcc_dev_lift_inverse"):
+        getattr(lib, name).argtypes = [vp, vp, i32, i64p, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     # unique-position quantisation and the source partitions of a batch of slices
     lib.gpcc_quantize_positions.argtypes = [vp, C.POINTER(QuantizeParams), vp, i32, vp, vp, vp, C.POINTER(i32)]
     lib.gpcc_src_partition.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.c_int64, i64p]

@@ -59,6 +59,7 @@
 #include "ref_crop.hpp"
 #include "symbol_stream.hpp"
 #include "raht_marshal.hpp"
+#include "lift_batch.hpp"
 
 using namespace gpcc;
 
@@ -1959,45 +1960,7 @@ launch_lift(
   cx.num_lods = p->num_lods;
   for (int l = 0; l < p->num_lods; l++)
     cx.npl[l] = p->num_points_in_lod[l];
-  // replay the reference's running counters over the distinct LoD
-  // boundaries (AttributeEncoder.cpp:1430-1440)
-  {
-    int ql = 0, lod = 0, nr = 0;
-    cx.range_start[nr] = 0;
-    cx.range_qlayer[nr] = 0;
-    cx.range_lcp[nr] = 0;
-    nr++;
-    int prev = -1;
-    for (int l = 0; l < p->num_lods; l++) {
-      const int b = p->num_points_in_lod[l];
-      if (b == prev || b >= n || b == 0) {
-        prev = b;
-        if (b == 0) {
-          // index 0 itself is a boundary: the counters step before the
-          // first coefficient
-          if (cx.range_start[0] == 0 && nr == 1) {
-            if (0 == p->num_points_in_lod[ql])
-              ql = std::min(p->num_qp_layers - 1, ql + 1);
-            if (lod < p->num_lods && 0 == p->num_points_in_lod[lod])
-              lod++;
-            cx.range_qlayer[0] = ql;
-            cx.range_lcp[0] = lod;
-          }
-        }
-        continue;
-      }
-      prev = b;
-      if (b == p->num_points_in_lod[ql])
-        ql = std::min(p->num_qp_layers - 1, ql + 1);
-      if (lod < p->num_lods && b == p->num_points_in_lod[lod])
-        lod++;
-      cx.range_start[nr] = b;
-      cx.range_qlayer[nr] = ql;
-      cx.range_lcp[nr] = std::min(lod, GPCC_MAX_LODS - 1);
-      nr++;
-    }
-    cx.num_ranges = nr;
-  }
+  cx.num_ranges = lift_replay_ranges(p, n, cx.range_start, cx.range_qlayer, cx.range_lcp);
   cx.lcp_enabled = p->last_component_prediction_enabled_flag && C == 3;
   cx.bitdepth = p->bitdepth;
   cx.num_qp_layers = p->num_qp_layers;
@@ -6311,9 +6274,139 @@ dev_inter_coder_attr(
   });
 }
 
+// The lifting transform of a batch over the LoD structures the caller holds in HBM (lift_batch.hpp): one upload
+// of the tables, the batch's kernels, one wait.  The refusals are decided ahead of the context and of any launch.
+int
+dev_lift_batch(
+  gpcc_ctx* ctx, bool encoder, const gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets,
+  const int32_t* d_nc, const int32_t* d_ni, const int32_t* d_nw, const int32_t* d_indexes, const int32_t* d_xyz,
+  int32_t* d_attrs, int32_t* d_coeffs, int8_t* lcp_coeffs, int32_t c)
+{
+  if (!lift || !d_nc || !d_ni || !d_nw || !d_indexes || !d_attrs || !d_coeffs)
+    return fail(GPCC_ERR_INVALID_ARG, "null buffer");
+  int r = check_batch_offsets(num_slices, offsets);
+  if (r)
+    return r;
+  if (num_slices > kLiftBatchMaxSlices)
+    return fail(GPCC_ERR_INVALID_ARG, "more than 2^18 slices per batch");
+  if (c < 1 || c > 3)
+    return fail(GPCC_ERR_INVALID_ARG, "attribute count not 1..3");
+  for (int s = 0; s < num_slices; s++) {
+    const gpcc_lift_params& p = lift[s];
+    r = check_lift_params(&p, (int)(offsets[s + 1] - offsets[s]), c);
+    if (r)
+      return r;
+    if (p.num_points_in_lod[0] < 0)
+      return fail(GPCC_ERR_INVALID_ARG, "num_points_in_lod negative");
+    if (p.bitdepth < 1 || p.bitdepth > 16)
+      return fail(GPCC_ERR_INVALID_ARG, "bitdepth outside [1, 16]");
+    if (p.num_qp_regions < 0 || p.num_qp_regions > GPCC_MAX_QP_REGIONS)
+      return fail(GPCC_ERR_INVALID_ARG, "num_qp_regions out of range");
+    if (p.num_qp_regions > 0 && !d_xyz)
+      return fail(GPCC_ERR_INVALID_ARG, "a slice names QP regions and d_xyz is null");
+    if (p.last_component_prediction_enabled_flag && c == 3 && !lcp_coeffs)
+      return fail(GPCC_ERR_INVALID_ARG, "lcp_coeffs is null");
+  }
+  if (!ctx)
+    return fail(GPCC_ERR_INVALID_ARG, "ctx is null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  LiftBatchPlan plan;
+  lift_batch_plan(plan, lift, num_slices, offsets, c, encoder ? nullptr : lcp_coeffs);
+  const size_t S = (size_t)num_slices, N = (size_t)plan.n;
+
+  // the largest first: the pool's best fit then finds every block of the previous call of this shape again
+  PoolScope pool(ctx);
+  LiftBatch b{};
+  char* d_meta = nullptr;
+  struct Want {
+    size_t bytes;
+    void** out;
+  } want[6] = {
+    {sizeof(int64_t) * N * c, (void**)&b.a},
+    {sizeof(unsigned long long) * N * c, (void**)&b.up},
+    {sizeof(unsigned long long) * N, (void**)&b.qw},
+    {sizeof(unsigned long long) * N, (void**)&b.uw},
+    {sizeof(long long) * 2 * GPCC_MAX_LODS * S, (void**)&b.lcp_sums},
+    {plan.meta.size(), (void**)&d_meta},
+  };
+  std::stable_sort(want, want + 6, [](const Want& x, const Want& y) { return x.bytes > y.bytes; });
+  for (const Want& w : want)
+    HIP_TRY(pool.take_bytes(w.bytes, w.out));
+
+  // what comes back with the one wait, through pinned memory: the verdict and, for the encoder, the slices' LCP
+  // coefficients -- the context's small block, for a batch of thousands of slices its bounce buffer
+  const size_t lcp_bytes = encoder && plan.any_lcp ? S * GPCC_MAX_LODS : 0;
+  HIP_TRY(h2d_user(ctx, d_meta, plan.meta.data(), plan.meta.size(), st));
+  HIP_TRY(small_reset(ctx));
+  char* h = (char*)small_slot(ctx, 64 + lcp_bytes);
+  if (!h) {
+    // (no wait for the upload that may still be leaving the buffer: the results arrive on the same stream, behind it)
+    HIP_TRY(bounce_ready(ctx));
+    h = (char*)ctx->h_bounce;
+  }
+
+  lift_batch_view(b, plan, d_meta);
+  b.nc = d_nc;
+  b.ni = d_ni;
+  b.nw = d_nw;
+  b.indexes = d_indexes;
+  b.xyz = d_xyz;
+  b.attrs = d_attrs;
+  b.coeffs = d_coeffs;
+  b.rsqrt = &ctx->d_lut->rsqrt;
+  auto span = [&](const char* name) { return Timer(ctx, name); };
+  HIP_TRY(lift_batch_launch(st, b, plan, d_meta, encoder, span));
+
+  HIP_TRY(hipMemcpyAsync(h, b.verdict, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (lcp_bytes)
+    HIP_TRY(hipMemcpyAsync(h + 64, b.lcp, lcp_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (*(const int32_t*)h)
+    return fail(
+      GPCC_ERR_INVALID_ARG,
+      "bad neighbour count / index table, or lifting: a neighbour is not in a coarser level of detail than its "
+      "predictor; nothing was written");
+  for (size_t s = 0; lcp_bytes && s < S; s++)
+    if (lift[s].last_component_prediction_enabled_flag)
+      memcpy(lcp_coeffs + s * GPCC_MAX_LODS, h + 64 + s * GPCC_MAX_LODS, GPCC_MAX_LODS);
+  return GPCC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int
+gpcc_dev_lift_forward(
+  gpcc_ctx* ctx, const gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets, const void* d_neigh_count,
+  const void* d_neigh_index, const void* d_neigh_weight, const void* d_indexes, const void* d_xyz, void* d_attrs,
+  void* d_coeffs, int8_t* lcp_coeffs, int32_t c)
+{
+  return counted(
+    ctx,
+    dev_lift_batch(
+      ctx, true, lift, num_slices, offsets, (const int32_t*)d_neigh_count, (const int32_t*)d_neigh_index,
+      (const int32_t*)d_neigh_weight, (const int32_t*)d_indexes, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)d_coeffs, lcp_coeffs, c),
+    batch_points(offsets, num_slices));
+}
+
+int
+gpcc_dev_lift_inverse(
+  gpcc_ctx* ctx, const gpcc_lift_params* lift, int32_t num_slices, const int64_t* offsets, const void* d_neigh_count,
+  const void* d_neigh_index, const void* d_neigh_weight, const void* d_indexes, const void* d_xyz, void* d_attrs,
+  const void* d_coeffs, const int8_t* lcp_coeffs, int32_t c)
+{
+  return counted(
+    ctx,
+    dev_lift_batch(
+      ctx, false, lift, num_slices, offsets, (const int32_t*)d_neigh_count, (const int32_t*)d_neigh_index,
+      (const int32_t*)d_neigh_weight, (const int32_t*)d_indexes, (const int32_t*)d_xyz, (int32_t*)d_attrs,
+      (int32_t*)const_cast<void*>(d_coeffs), const_cast<int8_t*>(lcp_coeffs), c),
+    batch_points(offsets, num_slices));
+}
 
 int
 gpcc_dev_lod_build(

@@ -55,6 +55,51 @@ struct LiftCtx {
   const RsqrtLut* rsqrt;   // device copy of the rsqrt tables
 };
 
+// The reference's running `quantLayer` / `lod` counters over the distinct LoD boundaries of a slice of
+// n points (a replay of AttributeEncoder.cpp:1430-1440, on the host): range_start / range_qlayer /
+// range_lcp [kMaxLodRanges] -> the number of ranges.  launch_lift and the batch's slice table
+// (lift_batch.hpp) both take their ranges from here.
+inline int
+lift_replay_ranges(const gpcc_lift_params* p, int n, int32_t* range_start, int32_t* range_qlayer, int32_t* range_lcp)
+{
+  const int last_layer = p->num_qp_layers - 1;
+  int ql = 0, lod = 0, nr = 0;
+  range_start[nr] = 0;
+  range_qlayer[nr] = 0;
+  range_lcp[nr] = 0;
+  nr++;
+  int prev = -1;
+  for (int l = 0; l < p->num_lods; l++) {
+    const int b = p->num_points_in_lod[l];
+    if (b == prev || b >= n || b == 0) {
+      prev = b;
+      if (b == 0) {
+        // index 0 itself is a boundary: the counters step before the
+        // first coefficient
+        if (range_start[0] == 0 && nr == 1) {
+          if (0 == p->num_points_in_lod[ql])
+            ql = last_layer < ql + 1 ? last_layer : ql + 1;
+          if (lod < p->num_lods && 0 == p->num_points_in_lod[lod])
+            lod++;
+          range_qlayer[0] = ql;
+          range_lcp[0] = lod;
+        }
+      }
+      continue;
+    }
+    prev = b;
+    if (b == p->num_points_in_lod[ql])
+      ql = last_layer < ql + 1 ? last_layer : ql + 1;
+    if (lod < p->num_lods && b == p->num_points_in_lod[lod])
+      lod++;
+    range_start[nr] = b;
+    range_qlayer[nr] = ql;
+    range_lcp[nr] = lod < GPCC_MAX_LODS - 1 ? lod : GPCC_MAX_LODS - 1;
+    nr++;
+  }
+  return nr;
+}
+
 __device__ __forceinline__ int64_t
 div_exp2_round_half_inf(int64_t x, int s)
 {
@@ -150,19 +195,221 @@ lod_blend_weights_kernel(
   }
 }
 
+// ---- the arithmetic of one predictor / one coefficient ----------------------------------------
+// The kernels below walk ONE slice; those of lift_batch.hpp walk the slices of a batch.  Both call
+// these bodies with the arrays of the slice the predictor belongs to (neighbour indices are slice
+// relative), so the arithmetic is stated once.
+
+// working values of predictor i: weight 1, empty update sums, the source attribute in fixed point
+__device__ __forceinline__ void
+lift_init_point(
+  int c, int encoder, const int32_t* attrs, const int32_t* indexes, int64_t* a, unsigned long long* qw,
+  unsigned long long* uw, unsigned long long* up, int i)
+{
+  qw[i] = 256;
+  uw[i] = 0;
+  for (int k = 0; k < c; k++) {
+    up[(size_t)i * c + k] = 0;
+    a[(size_t)i * c + k] = encoder ? (int64_t)attrs[(size_t)indexes[i] * c + k] * 256 : 0;
+  }
+}
+
+// PCCComputeQuantizationWeights, predictor i
+__device__ __forceinline__ void
+lift_quant_weights_point(
+  const int32_t* nc, const int32_t* ni, const int32_t* nw, unsigned long long* qw, int i)
+{
+  const unsigned long long q = qw[i];
+  const int cnt = nc[i];
+  for (int j = 0; j < cnt; j++)
+    atomicAdd(&qw[ni[3 * (size_t)i + j]], ((unsigned long long)(uint32_t)nw[3 * (size_t)i + j] * q + 128) >> 8);
+}
+
+// computeQuantizationWeightsScalable (PCCTMC3Common.h:858-891), predictor i of a whole slice of n points
+__device__ __forceinline__ unsigned long long
+quant_weight_scalable_point(int n, int num_lods, const int32_t* npl, int i)
+{
+  int l = 0;
+  while (l < num_lods - 1 && npl[l] <= i)
+    l++;
+  return l == num_lods - 1 ? 256ull : (unsigned long long)(n / npl[l]) << 8;
+}
+
+// PCCLiftPredict, predictor i
+template<int C>
+__device__ __forceinline__ void
+lift_predict_point(const int32_t* nc, const int32_t* ni, const int32_t* nw, int64_t* a, int i, int direct)
+{
+  int64_t pred[C];
+#pragma unroll
+  for (int k = 0; k < C; k++)
+    pred[k] = 0;
+  const int cnt = nc[i];
+  for (int j = 0; j < cnt; j++) {
+    const int64_t w = (uint32_t)nw[3 * (size_t)i + j];
+    const size_t nb = ni[3 * (size_t)i + j];
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      pred[k] += w * a[nb * C + k];
+  }
+#pragma unroll
+  for (int k = 0; k < C; k++) {
+    const int64_t p = div_exp2_round_half_inf(pred[k], 8);
+    a[(size_t)i * C + k] += direct ? -p : p;
+  }
+}
+
+// PCCLiftUpdate, the scatter of predictor i into its receivers
+template<int C>
+__device__ __forceinline__ void
+lift_update_scatter_point(
+  const int32_t* nc, const int32_t* ni, const int32_t* nw, const unsigned long long* qw, unsigned long long* uw,
+  unsigned long long* up, const int64_t* a, int i)
+{
+  const unsigned long long q = qw[i];
+  const int cnt = nc[i];
+  for (int j = 0; j < cnt; j++) {
+    const unsigned long long w = ((unsigned long long)(uint32_t)nw[3 * (size_t)i + j] * q + 128) >> 8;
+    const size_t nb = ni[3 * (size_t)i + j];
+    atomicAdd(&uw[nb], w);
+#pragma unroll
+    for (int k = 0; k < C; k++)
+      atomicAdd(&up[nb * C + k], w * (unsigned long long)a[(size_t)i * C + k]);
+  }
+}
+
+// PCCLiftUpdate, receiver i: one divApprox, the accumulators cleared for the next LoD
+template<int C>
+__device__ __forceinline__ void
+lift_update_apply_point(unsigned long long* uw, unsigned long long* up, int64_t* a, int i, int direct)
+{
+  const uint32_t sum = (uint32_t)uw[i];  // truncated as in the reference (:813)
+  if (uw[i])
+    uw[i] = 0;
+#pragma unroll
+  for (int k = 0; k < C; k++) {
+    const int64_t u = (int64_t)up[(size_t)i * C + k];
+    if (u)
+      up[(size_t)i * C + k] = 0;
+    if (sum) {
+      const int64_t v = div_approx(u, sum, 0);
+      a[(size_t)i * C + k] += direct ? v : -v;
+    }
+  }
+}
+
+// the two products of computeLastComponentPredictionCoeff (:1498-1539) for coefficient i
+__device__ __forceinline__ void
+lift_lcp_products(const int64_t* a, int i, long long& m12, long long& m11)
+{
+  const int64_t k1 = a[(size_t)i * 3 + 1], k2 = a[(size_t)i * 3 + 2];
+  // NB: the reference truncates both products to int before summing
+  m12 = (int32_t)(k1 * k2);
+  m11 = (int32_t)(k1 * k1);
+}
+
+// ... and its coefficients from the per-LoD sums [num_lods][2] of a slice: a replay of the sequential loop
+// over coefficients -- the sums accumulate until an index equals numPointsInLod[lod] - 1
+__device__ __forceinline__ void
+lift_lcp_resolve(int num_lods, const int32_t* npl, const long long* lcp_sums, int8_t* lcp)
+{
+  long long s12 = 0, s11 = 0;
+  int lod = 0;
+  int8_t signs[GPCC_MAX_LODS];
+  for (int l = 0; l < GPCC_MAX_LODS; l++)
+    signs[l] = 0;
+  int prev_end = 0;
+  for (int l = 0; l < num_lods; l++) {
+    const int end = npl[l];
+    if (end == prev_end)
+      continue;  // empty LoD: no coefficient index falls here
+    s12 += lcp_sums[2 * l];
+    s11 += lcp_sums[2 * l + 1];
+    prev_end = end;
+    if (lod < num_lods && end == npl[lod]) {
+      int scale = 0;
+      if (s12 && s11) {
+        const int sign = ((s12 < 0) ^ (s11 < 0)) ? -1 : 1;
+        scale = (int)(((s12 << 2) + sign * (s11 >> 1)) / s11);
+      }
+      s12 = s11 = 0;
+      signs[lod++] = (int8_t)clip(scale, -8, 8);
+    }
+  }
+  for (; lod < GPCC_MAX_LODS; lod++)
+    signs[lod] = lod ? signs[lod - 1] : 0;
+  for (int l = 0; l < GPCC_MAX_LODS; l++)
+    lcp[l] = signs[l];
+}
+
+// which of the ranges between distinct LoD boundaries holds coefficient i
+__device__ __forceinline__ int
+lift_range_of(int num_ranges, const int32_t* range_start, int i)
+{
+  int r = 0;
+  while (r + 1 < num_ranges && i >= range_start[r + 1])
+    r++;
+  return r;
+}
+
+// quantisation and reconstruction of coefficient i (col: its working values, val: its coefficients):
+// lqp the QP pair of its layer, (o0, o1) the region offsets of its point, lcpc its last-component
+// prediction coefficient, w its quantisation weight
+template<int C>
+__device__ __forceinline__ void
+lift_quantise_point(
+  int encoder, const int32_t* lqp, int o0, int o1, int max_qp, int fixed_point_qp_offset, int lcpc, uint64_t w,
+  const RsqrtLut& lut, int64_t* col, int32_t* val)
+{
+  const int qp0 = clip(lqp[0] + o0, 4, max_qp);
+  const int qp1 = clip(lqp[1] + o1 + qp0, 4, max_qp);
+  const Quantizer q0 = make_quantizer(qp0 + fixed_point_qp_offset);
+  const Quantizer q1 = make_quantizer(qp1 + fixed_point_qp_offset);
+  const int64_t iqw = (int64_t)irsqrt(w, lut);
+  const int64_t qwt = (int64_t)((w * (uint64_t)iqw + ((uint64_t)1 << 39)) >> 40);
+  int32_t v0 = encoder ? (int32_t)quantize(q0, col[0] * qwt) : val[0];
+  int64_t scaled = (int64_t)v0 * q0.step;
+  col[0] = div_exp2_round_half_inf(scaled * iqw, 40);
+  if (encoder)
+    val[0] = v0;
+  if (C >= 2) {
+    int32_t v1 = encoder ? (int32_t)quantize(q1, col[1] * qwt) : val[1];
+    scaled = (int64_t)v1 * q1.step;
+    col[1] = div_exp2_round_half_inf(scaled * iqw, 40);
+    if (encoder)
+      val[1] = v1;
+  }
+  if (C == 3) {
+    if (encoder)
+      col[2] -= ((int64_t)lcpc * col[1]) >> 2;
+    scaled *= lcpc;
+    scaled >>= 2;
+    int32_t v2 = encoder ? (int32_t)quantize(q1, col[2] * qwt) : val[2];
+    scaled += (int64_t)v2 * q1.step;
+    col[2] = div_exp2_round_half_inf(scaled * iqw, 40);
+    if (encoder)
+      val[2] = v2;
+  }
+}
+
+// the reconstruction of predictor i, rounded and clipped, to its point
+__device__ __forceinline__ void
+lift_writeback_point(int c, int64_t clip_max, const int64_t* a, const int32_t* indexes, int32_t* attrs, int i)
+{
+  const size_t pt = indexes[i];
+  for (int k = 0; k < c; k++) {
+    int64_t v = div_exp2_round_half_inf(a[(size_t)i * c + k], 8);
+    v = v < 0 ? 0 : (v > clip_max ? clip_max : v);
+    attrs[pt * c + k] = (int32_t)v;
+  }
+}
+
 __global__ __launch_bounds__(256) void
 lift_init_kernel(LiftCtx cx, int encoder)
 {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cx.n;
-       i += gridDim.x * blockDim.x) {
-    cx.qw[i] = 256;
-    cx.uw[i] = 0;
-    for (int k = 0; k < cx.c; k++) {
-      cx.up[(size_t)i * cx.c + k] = 0;
-      cx.a[(size_t)i * cx.c + k] =
-        encoder ? (int64_t)cx.attrs[(size_t)cx.indexes[i] * cx.c + k] * 256 : 0;
-    }
-  }
+       i += gridDim.x * blockDim.x)
+    lift_init_point(cx.c, encoder, cx.attrs, cx.indexes, cx.a, cx.qw, cx.uw, cx.up, i);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 2 * GPCC_MAX_LODS;
        i += gridDim.x * blockDim.x)
     cx.lcp_sums[i] = 0;
@@ -173,14 +420,8 @@ __global__ __launch_bounds__(256) void
 lift_quant_weights_kernel(LiftCtx cx, int start, int end)
 {
   for (int i = start + blockIdx.x * blockDim.x + threadIdx.x; i < end;
-       i += gridDim.x * blockDim.x) {
-    const unsigned long long q = cx.qw[i];
-    const int cnt = cx.nc[i];
-    for (int j = 0; j < cnt; j++)
-      atomicAdd(
-        &cx.qw[cx.ni[3 * (size_t)i + j]],
-        ((unsigned long long)(uint32_t)cx.nw[3 * (size_t)i + j] * q + 128) >> 8);
-  }
+       i += gridDim.x * blockDim.x)
+    lift_quant_weights_point(cx.nc, cx.ni, cx.nw, cx.qw, i);
 }
 
 // computeQuantizationWeightsScalable (PCCTMC3Common.h:858-891) of a whole slice:
@@ -194,12 +435,8 @@ struct LodSizes {
 __global__ __launch_bounds__(256) void
 quant_weights_scalable_kernel(int n, LodSizes t, unsigned long long* qw)
 {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l < t.num_lods - 1 && t.npl[l] <= i)
-      l++;
-    qw[i] = l == t.num_lods - 1 ? 256ull : (unsigned long long)(n / t.npl[l]) << 8;
-  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    qw[i] = quant_weight_scalable_point(n, t.num_lods, t.npl, i);
 }
 
 // The same for a partially decoded slice (minGeomNodeSizeLog2 > 0): the numerator
@@ -225,25 +462,8 @@ __global__ __launch_bounds__(256) void
 lift_predict_kernel(LiftCtx cx, int start, int end, int direct)
 {
   for (int i = start + blockIdx.x * blockDim.x + threadIdx.x; i < end;
-       i += gridDim.x * blockDim.x) {
-    int64_t pred[C];
-#pragma unroll
-    for (int k = 0; k < C; k++)
-      pred[k] = 0;
-    const int cnt = cx.nc[i];
-    for (int j = 0; j < cnt; j++) {
-      const int64_t w = (uint32_t)cx.nw[3 * (size_t)i + j];
-      const size_t nb = cx.ni[3 * (size_t)i + j];
-#pragma unroll
-      for (int k = 0; k < C; k++)
-        pred[k] += w * cx.a[nb * C + k];
-    }
-#pragma unroll
-    for (int k = 0; k < C; k++) {
-      const int64_t p = div_exp2_round_half_inf(pred[k], 8);
-      cx.a[(size_t)i * C + k] += direct ? -p : p;
-    }
-  }
+       i += gridDim.x * blockDim.x)
+    lift_predict_point<C>(cx.nc, cx.ni, cx.nw, cx.a, i, direct);
 }
 
 template<int C>
@@ -251,19 +471,8 @@ __global__ __launch_bounds__(256) void
 lift_update_scatter_kernel(LiftCtx cx, int start, int end)
 {
   for (int i = start + blockIdx.x * blockDim.x + threadIdx.x; i < end;
-       i += gridDim.x * blockDim.x) {
-    const unsigned long long q = cx.qw[i];
-    const int cnt = cx.nc[i];
-    for (int j = 0; j < cnt; j++) {
-      const unsigned long long w =
-        ((unsigned long long)(uint32_t)cx.nw[3 * (size_t)i + j] * q + 128) >> 8;
-      const size_t nb = cx.ni[3 * (size_t)i + j];
-      atomicAdd(&cx.uw[nb], w);
-#pragma unroll
-      for (int k = 0; k < C; k++)
-        atomicAdd(&cx.up[nb * C + k], w * (unsigned long long)cx.a[(size_t)i * C + k]);
-    }
-  }
+       i += gridDim.x * blockDim.x)
+    lift_update_scatter_point<C>(cx.nc, cx.ni, cx.nw, cx.qw, cx.uw, cx.up, cx.a, i);
 }
 
 template<int C>
@@ -271,21 +480,8 @@ __global__ __launch_bounds__(256) void
 lift_update_apply_kernel(LiftCtx cx, int start, int direct)
 {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < start;
-       i += gridDim.x * blockDim.x) {
-    const uint32_t sum = (uint32_t)cx.uw[i];  // truncated as in the reference (:813)
-    if (cx.uw[i])
-      cx.uw[i] = 0;
-#pragma unroll
-    for (int k = 0; k < C; k++) {
-      const int64_t u = (int64_t)cx.up[(size_t)i * C + k];
-      if (u)
-        cx.up[(size_t)i * C + k] = 0;
-      if (sum) {
-        const int64_t v = div_approx(u, sum, 0);
-        cx.a[(size_t)i * C + k] += direct ? v : -v;
-      }
-    }
-  }
+       i += gridDim.x * blockDim.x)
+    lift_update_apply_point<C>(cx.uw, cx.up, cx.a, i, direct);
 }
 
 // per-LoD sums of computeLastComponentPredictionCoeff (:1498-1539)
@@ -301,10 +497,7 @@ lift_lcp_sums_kernel(LiftCtx cx)
     long long m12 = 0, m11 = 0;
     int l = 0;
     if (valid) {
-      const int64_t k1 = cx.a[(size_t)i * 3 + 1], k2 = cx.a[(size_t)i * 3 + 2];
-      // NB: the reference truncates both products to int before summing
-      m12 = (int32_t)(k1 * k2);
-      m11 = (int32_t)(k1 * k1);
+      lift_lcp_products(cx.a, i, m12, m11);
       while (l < cx.num_lods - 1 && i >= cx.npl[l])
         l++;
     }
@@ -334,35 +527,7 @@ lift_lcp_resolve_kernel(LiftCtx cx)
 {
   if (blockIdx.x || threadIdx.x)
     return;
-  // replay of the sequential loop over coefficients on per-LoD sums: the
-  // sums accumulate until an index equals numPointsInLod[lod] - 1
-  long long s12 = 0, s11 = 0;
-  int lod = 0;
-  int8_t signs[GPCC_MAX_LODS];
-  for (int l = 0; l < GPCC_MAX_LODS; l++)
-    signs[l] = 0;
-  int prev_end = 0;
-  for (int l = 0; l < cx.num_lods; l++) {
-    const int end = cx.npl[l];
-    if (end == prev_end)
-      continue;  // empty LoD: no coefficient index falls here
-    s12 += cx.lcp_sums[2 * l];
-    s11 += cx.lcp_sums[2 * l + 1];
-    prev_end = end;
-    if (lod < cx.num_lods && end == cx.npl[lod]) {
-      int scale = 0;
-      if (s12 && s11) {
-        const int sign = ((s12 < 0) ^ (s11 < 0)) ? -1 : 1;
-        scale = (int)(((s12 << 2) + sign * (s11 >> 1)) / s11);
-      }
-      s12 = s11 = 0;
-      signs[lod++] = (int8_t)clip(scale, -8, 8);
-    }
-  }
-  for (; lod < GPCC_MAX_LODS; lod++)
-    signs[lod] = lod ? signs[lod - 1] : 0;
-  for (int l = 0; l < GPCC_MAX_LODS; l++)
-    cx.lcp[l] = signs[l];
+  lift_lcp_resolve(cx.num_lods, cx.npl, cx.lcp_sums, cx.lcp);
 }
 
 template<int C>
@@ -378,46 +543,14 @@ lift_quantise_kernel(LiftCtx cx, int encoder)
   __syncthreads();
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cx.n;
        i += gridDim.x * blockDim.x) {
-    int r = 0;
-    while (r + 1 < cx.num_ranges && i >= cx.range_start[r + 1])
-      r++;
-    const int layer = cx.range_qlayer[r];
+    const int r = lift_range_of(cx.num_ranges, cx.range_start, i);
     const int lcpc = (C == 3 && cx.lcp_enabled) ? cx.lcp[cx.range_lcp[r]] : 0;
     const int pt = cx.indexes[i];
     const int o0 = cx.qp_off ? cx.qp_off[2 * (size_t)pt] : 0;
     const int o1 = cx.qp_off ? cx.qp_off[2 * (size_t)pt + 1] : 0;
-    const int qp0 = clip(cx.layer_qp[layer][0] + o0, 4, cx.max_qp);
-    const int qp1 = clip(cx.layer_qp[layer][1] + o1 + qp0, 4, cx.max_qp);
-    const Quantizer q0 = make_quantizer(qp0 + cx.fixed_point_qp_offset);
-    const Quantizer q1 = make_quantizer(qp1 + cx.fixed_point_qp_offset);
-    const uint64_t w = cx.qw[i];
-    const int64_t iqw = (int64_t)irsqrt(w, lut);
-    const int64_t qwt = (int64_t)((w * (uint64_t)iqw + ((uint64_t)1 << 39)) >> 40);
-    int64_t* col = &cx.a[(size_t)i * C];
-    int32_t* val = &cx.coeffs[(size_t)i * C];
-    int32_t v0 = encoder ? (int32_t)quantize(q0, col[0] * qwt) : val[0];
-    int64_t scaled = (int64_t)v0 * q0.step;
-    col[0] = div_exp2_round_half_inf(scaled * iqw, 40);
-    if (encoder)
-      val[0] = v0;
-    if (C >= 2) {
-      int32_t v1 = encoder ? (int32_t)quantize(q1, col[1] * qwt) : val[1];
-      scaled = (int64_t)v1 * q1.step;
-      col[1] = div_exp2_round_half_inf(scaled * iqw, 40);
-      if (encoder)
-        val[1] = v1;
-    }
-    if (C == 3) {
-      if (encoder)
-        col[2] -= ((int64_t)lcpc * col[1]) >> 2;
-      scaled *= lcpc;
-      scaled >>= 2;
-      int32_t v2 = encoder ? (int32_t)quantize(q1, col[2] * qwt) : val[2];
-      scaled += (int64_t)v2 * q1.step;
-      col[2] = div_exp2_round_half_inf(scaled * iqw, 40);
-      if (encoder)
-        val[2] = v2;
-    }
+    lift_quantise_point<C>(
+      encoder, cx.layer_qp[cx.range_qlayer[r]], o0, o1, cx.max_qp, cx.fixed_point_qp_offset, lcpc, cx.qw[i], lut,
+      &cx.a[(size_t)i * C], &cx.coeffs[(size_t)i * C]);
   }
 }
 
@@ -426,14 +559,8 @@ lift_writeback_kernel(LiftCtx cx)
 {
   const int64_t clip_max = ((int64_t)1 << cx.bitdepth) - 1;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cx.n;
-       i += gridDim.x * blockDim.x) {
-    const size_t pt = cx.indexes[i];
-    for (int k = 0; k < cx.c; k++) {
-      int64_t v = div_exp2_round_half_inf(cx.a[(size_t)i * cx.c + k], 8);
-      v = v < 0 ? 0 : (v > clip_max ? clip_max : v);
-      cx.attrs[pt * cx.c + k] = (int32_t)v;
-    }
-  }
+       i += gridDim.x * blockDim.x)
+    lift_writeback_point(cx.c, clip_max, cx.a, cx.indexes, cx.attrs, i);
 }
 
 // QP regions of a slice (the qp_region_* fields of gpcc_lift_params / gpcc_pred_params) -> the region

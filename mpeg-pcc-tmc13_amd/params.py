@@ -182,6 +182,16 @@ def lift_params(num_points_in_lod, qp=34, chroma_offset=-1, bitdepth=8, lcp=True
     return p
 
 
+def lift_params_of_lod(num_points_in_lod, regions=None, **kw):
+    """a LiftParams for one slice of a batch from its row of what Context.dev_lod_build returns (the cumulative LoD
+    sizes), for Context.dev_lift; kw: as lift_params (QP, bit depth, LCP, layers, scalable); regions: as
+    set_qp_regions, the slice's own boxes"""
+    p = lift_params(num_points_in_lod, **kw)
+    if regions:
+        set_qp_regions(p, regions)
+    return p
+
+
 class PredParams(C.Structure):
     """ctypes mirror of gpcc_pred_params."""
     _fields_ = [

@@ -760,6 +760,22 @@ class Context:
             C.memmove(C.byref(lift_params_list[i]), C.byref(arr[i]), C.sizeof(LiftParams))
         return l
 
+    def dev_lift(self, forward, lift_params_list, offsets, d_count, d_index, d_weight, d_indexes, d_attrs, d_coeffs, c,
+                 lcp=None, d_xyz=None):
+        """gpcc_dev_lift_forward / _inverse: the lifting transform of a batch over the LoD structure dev_lod_build left
+        in d_count / d_index / d_weight / d_indexes.  lift_params_list: one LiftParams per slice
+        (params.lift_params_of_lod), input only; d_xyz: needed where a slice names QP regions.
+        -> lcp int8 [slices, 32] (forward: written for the slices with the flag; inverse: pass the forward's)"""
+        from .params import LiftParams
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        s = len(offs) - 1
+        arr = (LiftParams * s)(*lift_params_list)
+        l = np.zeros((s, 32), dtype=np.int8) if lcp is None else np.ascontiguousarray(lcp, dtype=np.int8).copy()
+        fn = self._lib.gpcc_dev_lift_forward if forward else self._lib.gpcc_dev_lift_inverse
+        _lib.check(fn(self._h, arr, s, offs.ctypes.data_as(C.POINTER(C.c_int64)), d_count, d_index, d_weight, d_indexes,
+                      d_xyz, d_attrs, d_coeffs, l.ctypes.data, c))
+        return l
+
     def zero_run_pack(self, coeffs, n, c, planar):
         """zero-run formation of the entropy loops -> (runs [m], values [m,c], trailing_run)"""
         co = np.ascontiguousarray(coeffs, dtype=np.int32).reshape(-1)
